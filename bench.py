@@ -1,6 +1,12 @@
 """bench.py -- PAVE-Net forward throughput on MI355X (clips/s), the BASELINE.json metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+    A plain run sets up, runs W warm-up and K timed steps and prints the headline line (with the roofline figures
+    the events inside the timed steps give); --full adds every other measurement and check below (the --gemm native
+    side leg, two batches in flight, the ATen census, the in-kernel clock pass, `extra` and the CPU oracle's
+    `cpu_baseline` / `parity`).  --dump-outputs DIR writes the last timed step's results (bboxes.npy, kpts.npy,
+    keep.npy) for output-for-output comparisons: with the same arguments the inputs and weights are the same seeded
+    ones in every run.
     N > 1 without a launcher (WORLD_SIZE unset): this process starts `python -m
     torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a CHILD
     process before anything touches the GPU (as the reference's tools/dist_test.sh:8-10 does with
@@ -105,6 +111,14 @@ def parse():
     ap.add_argument('--backbone', choices=('r50', 'hrnet_w48', 'swin_l'), default='r50',
                     help="'hrnet_w48' = BASELINE configs[3] (HRNet-w48 backbone under the MulFrames head); 'swin_l' = "
                          "the reference's 2025-2-7 Swin-L config (use --frames 3 --clips 1)")
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything besides the headline: the --gemm native side leg, two batches in '
+                         'flight, the un-timed census / clock passes, the other BASELINE configurations (`extra`) '
+                         'and the CPU oracle baseline + parity (the --no-* options above trim this set).  Without '
+                         'it a run sets up, warms up, times the --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the results of the last one as the caller receives them '
+                         '(bboxes [B, N, 5], kpts [B, N, K, 3], keep [B, N]; float32) to DIR/<name>.npy')
     ap.add_argument('--gemm', choices=('native', 'bf16x3', 'bf16x2', 'bf16', 'fp16'), default='bf16x3',
                     help="dense projections / convolutions: 'bf16x3' (the headline) = hand-written "
                          "exact 3-term bf16 split on the bf16 MFMA: fp32 in, fp32 accumulate, "
@@ -283,6 +297,19 @@ def clip0_image(args, frames):
     path see the same frames."""
     g = torch.Generator().manual_seed(0)
     return torch.randn(1, frames, 3, args.height, args.width, generator=g)
+
+
+def dump_outputs(directory, packed, N, K):
+    """--dump-outputs: the host results of the last timed step, [clips, N*5 + N*K*3 + N] as step() packs them, split
+    back into what forward_device returns for every clip of the step (a few KB per clip, float32)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    p = packed.float().numpy()
+    B = p.shape[0]
+    arrays = dict(bboxes=p[:, :N * 5].reshape(B, N, 5), kpts=p[:, N * 5:N * 5 + N * K * 3].reshape(B, N, K, 3),
+                  keep=p[:, N * 5 + N * K * 3:])
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline_and_parity(model, args, frames, clip0, free_result, free_selection=None):
@@ -750,7 +777,7 @@ def main():
         return dt, ev, out
 
     native_dt = None
-    if args.gemm != 'native' and graphed is None and not args.no_native_side and world == 1:
+    if args.full and args.gemm != 'native' and graphed is None and not args.no_native_side and world == 1:
         # the same workload on the vendor fp32-MFMA kernels, printed beside the headline
         set_gemm_mode('native')
         TAIL_ON[0] = False          # (the captured tail holds the headline mode's kernels)
@@ -761,10 +788,12 @@ def main():
         set_gemm_mode(args.gemm)
     dt, events, last = timed(True)
     last = last.clone()     # (the pinned result buffer is reused by later runs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, N, K)
     rank_dt = list(RANK_DT)
     ev_steps_main = (min(3, args.steps) if (graphed is None and not args.no_events) else 0)
     pipe_dt = None
-    if args.pipeline == 1 and world == 1 and graphed is None and not args.no_native_side:
+    if args.full and args.pipeline == 1 and world == 1 and graphed is None and not args.no_native_side:
         # the same K steps with two batches in flight (two HIP streams): throughput of a serving loop;
         # reported beside the headline, whose kernels run alone (clean per-kernel event times)
         TAIL_ON[0] = False
@@ -776,20 +805,20 @@ def main():
     # them: the census runs where the forward holds no collective -- every mode but the frame-sharded one --, the
     # clock pass, whose steps include the result all-gather, at N = 1 only)
     free_selection = None
-    if rank == 0 and shard is None and not args.no_extra_passes \
+    if args.full and rank == 0 and shard is None and not args.no_extra_passes \
             and hasattr(model.bbox_head.transformer, 'last_topk_proposals'):
         with torch.no_grad():      # (the un-pinned selections of clip 0, as the timed steps made them)
             r_ = model.forward_device(img, metas)
         free_selection = (model.bbox_head.transformer.last_topk_proposals[0].clone(), r_['score_index'][0].clone())
     census = None
-    if shard is None and not args.no_extra_passes:
+    if args.full and shard is None and not args.no_extra_passes:
         try:
             census = census_of_step(model, img, metas)
         except Exception as e:
             census = dict(census_error=f'{type(e).__name__}: {e}'[:200])
     clock = None
-    if dist is None and args.gemm != 'native' and graphed is None and tail_graph is None and not args.no_events \
-            and not args.no_extra_passes:
+    if args.full and dist is None and args.gemm != 'native' and graphed is None and tail_graph is None \
+            and not args.no_events and not args.no_extra_passes:
         clock = class_clock_pass(lambda: step())
     timed_ev = [(tag, s.elapsed_time(e) * 1e-3, fl) for tag, s, e, fl, _ in events]
     shaped_ev = [(tag, s.elapsed_time(e) * 1e-3, fl, sh) for tag, s, e, fl, sh in events]
@@ -958,10 +987,10 @@ def main():
                                       frac=round(tf / peak, 4),
                                       note='whole step incl. the non-MFMA kernels; peak = dense MFMA '
                                            'peak of the --gemm mode (in the split modes the Cin, Cout % 64 == 0 3x3 convolutions run on the same split kernel)')
-        if world == 1 and dist is None and not args.no_secondary and graphed is None and \
+        if args.full and world == 1 and dist is None and not args.no_secondary and graphed is None and \
                 args.backbone == 'r50' and (T, B) == (7, 4) and args.gemm == 'bf16x3':
             line['extra'] = secondary_workloads(args, dev)
-        if world == 1 and not args.no_cpu_baseline and clip0 is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and clip0 is not None:
             kept = last[0, -N:] > 0.5
             free_kpts = last[0, N * 5:N * 5 + N * K * 3].view(N, K, 3)[kept]
             line['cpu_baseline'], line['parity'] = cpu_baseline_and_parity(model, args, T, clip0,

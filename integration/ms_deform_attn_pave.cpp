@@ -7,8 +7,8 @@
 // DISPATCH_DEVICE_IMPL) run on the MI355X kernels.  It replaces the registrations of
 // csrc/pytorch/cuda/cudabind.cpp:736-765; on PyTorch-ROCm the device type is still `CUDA`.
 //
-// It is compiled (syntax + types, against the installed torch headers and the reference's own
-// pytorch_cpp_helper.hpp / pytorch_device_registry.hpp) by
+// It is compiled (syntax + types, against the installed torch headers and a stand-in of mmcv's
+// pytorch_cpp_helper.hpp / pytorch_device_registry.hpp that checks the registered signatures) by
 // tests/test_host_cpu.py::test_integration_binding_compiles, so INTEGRATION.md cannot rot.
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>  // the current stream on ROCm builds
 

@@ -4,7 +4,7 @@ Imports the real reference (zgspose/PAVENet at /root/reference) through
 oracle/ref_shim.py and writes small golden input/output vectors to
 tests/golden/*.npz.  The reference itself never travels; these vectors do.
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [op|modules|e2e|all]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [op|modules|e2e|pipeline|rescale|full|petr|configs|kpt2json|all]
 
 Parameters are never stored: both sides regenerate them with the name-seeded
 recipe in oracle/seeded.py from the (key -> shape) table kept in each file.
@@ -436,6 +436,53 @@ def gen_petr(which=None):
               det_labels=det_labels, det_kpts=det_kpts)
 
 
+REFERENCE_CONFIGS = {
+    'videopose_r50_t3': 'configs/videopose/2025-5-11/2025_5_11_res50_num_frames_3_posetrack17_layer_num_3.py',
+    'videopose_r50_t5': 'configs/videopose/2025-2-7/2025_2_7_res50_num_frames_5_posetrack17.py',
+    'videopose_swinl_t3': 'configs/videopose/2025-2-7/2025_2_7_swin_num_frames_3_posetrack17.py',
+    'petr_r50': 'configs/petr/petr_r50_16x2_100e_coco.py',
+    'petr_hrnetw48': 'configs/petr/petr_hrnetw48_16x2_100e_coco.py',
+    'vedpose_r50': 'configs/vedpose/single_frame_posetrack_resnet50_inference.py',
+}
+
+
+def gen_reference_configs():
+    """The `model` dict of six of the reference's config files as its own mmcv.Config resolves them (_base_
+    inheritance, overrides), for tests/test_host_cpu.py::test_reference_config_files_build."""
+    ref_shim.install()
+    from mmcv import Config
+    out = {name: Config.fromfile(os.path.join(ref_shim.REF, p)).model.to_dict()
+           for name, p in REFERENCE_CONFIGS.items()}
+    path = os.path.join(OUT, 'reference_model_configs.json')
+    open(path, 'w').write(json.dumps(out, indent=1, sort_keys=True) + '\n')
+    print('wrote', path, len(out), 'configs')
+
+
+def kpt2json_case():
+    """Input of the kpt2json golden (two images: two poses, none)."""
+    det = [np.array([[10., 20., 50., 80., 0.9], [1., 2., 3., 5., 0.4]], dtype=np.float32)]
+    kpt = [np.arange(2 * 15 * 3, dtype=np.float32).reshape(2, 15, 3)]
+    return [(det, kpt), ([np.zeros((0, 5), np.float32)], [np.zeros((0, 15, 3), np.float32)])]
+
+
+def gen_kpt2json():
+    """The reference dataset's own _kpt2json (opera/datasets/posetrack_video_pose.py) on kpt2json_case(), image ids
+    7 and 8, for tests/test_host_cpu.py::test_kpt2json_and_checkpoint_roundtrip."""
+    ref_shim.install()
+    from opera.datasets.posetrack_video_pose import PosetrackVideoPoseDataset as D
+
+    class Fake:
+        img_ids, cat_ids = [7, 8], [1]
+        xyxy2xywh = staticmethod(lambda b: [float(b[0]), float(b[1]), float(b[2] - b[0]), float(b[3] - b[1])])
+
+        def __len__(self):
+            return 2
+    bbox_json, kpt_json = D._kpt2json(Fake(), kpt2json_case())
+    path = os.path.join(OUT, 'kpt2json.json')
+    open(path, 'w').write(json.dumps(dict(bbox=bbox_json, keypoints=kpt_json)) + '\n')
+    print('wrote', path)
+
+
 if __name__ == '__main__':
     import logging
     logging.disable(logging.INFO)
@@ -454,3 +501,7 @@ if __name__ == '__main__':
         gen_fullsize()
     if what in ('petr', 'all'):
         gen_petr(sys.argv[2] if len(sys.argv) > 2 else None)
+    if what in ('configs', 'all'):
+        gen_reference_configs()
+    if what in ('kpt2json', 'all'):
+        gen_kpt2json()

@@ -44,7 +44,7 @@ def test_bench_world_branches_on_nccl_with_one_rank(shard):
     max-over-ranks all-reduce, barrier, teardown) with world = 1 on RCCL."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', 'nccl',
            '--steps', '2', '--warmup', '1', '--height', '128', '--width', '160', '--shard', shard,
-           '--frames', '5' if shard == 'frames' else '3', '--no-cpu-baseline', '--no-native-side',
+           '--frames', '5' if shard == 'frames' else '3', '--full', '--no-cpu-baseline', '--no-native-side',
            '--no-secondary', '--gemm-select', 'default']
     env = _env()
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):

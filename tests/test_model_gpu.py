@@ -1134,7 +1134,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(shard):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'),
            '--gpus', '2', '--steps', '2', '--warmup', '1', '--height', '128', '--width', '160',
-           '--shard', shard, '--frames', '5' if shard == 'frames' else '3', '--no-cpu-baseline',
+           '--shard', shard, '--frames', '5' if shard == 'frames' else '3', '--full', '--no-cpu-baseline',
            '--gemm-select', 'default']
     env = dict(os.environ, PAVE_BENCH_ONE_DEVICE='1')
     env.pop('WORLD_SIZE', None)
