@@ -40,7 +40,7 @@ extern "C" {
 #define PAVE_E_UNSUPPORTED (-4) /* valid arguments, but not a shape this entry point's kernel covers */
 
 /* ABI version; bumped on any signature change (pavenet_amd/native.py checks it at load). */
-#define PAVE_ABI_VERSION 20
+#define PAVE_ABI_VERSION 21
 int pave_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
 const char* pave_last_error(void);
@@ -339,6 +339,12 @@ int pave_ms_deform_attn_backward_f64(const double* value, const int64_t* spatial
 int pave_preprocess_frames(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
                            int Hn, int Wn, int Hp, int Wp, const float* mean, const float* std,
                            int to_rgb, void* stream);
+/* The same, mirrored within the resized width: dst[.., x] for x < Wn is what pave_preprocess_frames writes at
+ * Wn - 1 - x (bit for bit: the same arithmetic on the mirrored column); the padding stays zero on the right,
+ * as mmdet's RandomFlip (after Resize, before Normalize / Pad) leaves it. */
+int pave_preprocess_frames_flip(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
+                                int Hn, int Wn, int Hp, int Wp, const float* mean, const float* std,
+                                int to_rgb, void* stream);
 
 /*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
@@ -652,6 +658,45 @@ int pave_merge_softmax_partials_f32(const float* parts, float* out, int G, int U
 /* x[n] fp32 -> planes[nplanes][n] bf16: truncation terms, the last rounded to nearest even
  * (nplanes = 3: x = p0 + p1 + p2 exactly). */
 int pave_split_bf16x3_f32(const float* x, void* planes, long long n, int nplanes, void* stream);
+
+/*
+ * Test-time augmentation merge (opera/models/detectors/petr.py:118-187 aug_test / merge_aug_results ->
+ * mmdet multiclass_nms(return_inds=True) -> mmcv batched_nms -> nms_cpu / softnms_cpu), one launch, one
+ * workgroup per image.  The plan is copied into the kernel's arguments (no host->device copy).
+ *   bboxes[a] [B, N, 5] (x1, y1, x2, y2, score) and kpts[a] [B, N, K, 3] DEVICE: augmentation a's head results
+ *   keep[a]   [B, N] int32 DEVICE or NULL: rows with keep = 0 do not enter the merge (results_to_list's mask)
+ *   flip[a], img_w[a * B + b], scale_factor[a * B + b][4]: the augmentation's meta (horizontal flip only)
+ *   flip_perm [K]: the left/right permutation applied to flipped key points (out[k] = in[flip_perm[k]])
+ * Rows are concatenated augmentation-major, mapped back (flip, then / scale_factor), filtered by
+ * score > score_thr, and suppressed by method 0 = nms (ovr > iou_thr, descending score, equal scores: lower
+ * merged index first), 1 = soft naive, 2 = soft linear, 3 = soft gaussian (ovr >= iou_thr; sigma, min_score).
+ * Outputs, M = min(max_num, A N) (A N if max_num <= 0):
+ *   dets [B, M, 5] (soft-NMS: decayed scores), labels [B, M] int64 (0), kpts [B, M, K, 3] (score 1),
+ *   inds [B, M] int64 (rows of the concatenation, -1 past the end), keep [B, M] int32, count [B] int32.
+ * A N <= 4096 (the boxes live in LDS), A <= 16, A B <= 128, K <= 64.
+ */
+#define PAVE_AUG_MAX_AUGS 16
+#define PAVE_AUG_MAX_SLOTS 128
+#define PAVE_AUG_MAX_K 64
+typedef struct pave_aug_plan {
+  const float* bboxes[PAVE_AUG_MAX_AUGS];
+  const float* kpts[PAVE_AUG_MAX_AUGS];
+  const int32_t* keep[PAVE_AUG_MAX_AUGS];
+  int32_t flip[PAVE_AUG_MAX_AUGS];
+  float img_w[PAVE_AUG_MAX_SLOTS];
+  float scale_factor[PAVE_AUG_MAX_SLOTS][4];
+  int32_t flip_perm[PAVE_AUG_MAX_K];
+  int32_t n_aug, B, N, K;
+} pave_aug_plan;
+int pave_aug_merge_nms_f32(const pave_aug_plan* plan, float score_thr, int max_num, int method, float iou_thr,
+                           float sigma, float min_score, int offset, float* dets, int64_t* labels, float* kpts,
+                           int64_t* inds, int32_t* keep, int32_t* count, void* stream);
+
+/* Horizontal flip of preprocessed canvases x [n, C, Hp, Wp] -> y (out of place): columns [0, w) mirrored
+ * within themselves, w = valid_w[i] (DEVICE int32 [n]) or valid_w_all when valid_w is NULL; the columns
+ * from w on are copied unchanged. */
+int pave_hflip_canvas_f32(const float* x, float* y, const int32_t* valid_w, int valid_w_all, int n, int C, int Hp,
+                          int Wp, void* stream);
 
 #ifdef __cplusplus
 }

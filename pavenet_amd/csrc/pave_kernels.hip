@@ -1122,7 +1122,7 @@ __global__ __launch_bounds__(256) void preprocess_frames_kernel(
     const src_t* __restrict__ src, float* __restrict__ dst, const int T, const int H0,
     const int W0, const int Hn, const int Wn, const int Hp, const int Wp, const float m0,
     const float m1, const float m2, const float s0, const float s1, const float s2,
-    const int to_rgb) {
+    const int to_rgb, const int flip) {
 #pragma clang fp contract(off)   // every product and sum below is rounded on its own (no FMA)
   const long long n = (long long)T * Hp * Wp;
   // OpenCV's float INTER_LINEAR (mmcv.imresize -> cv2.resize on the to_float32 image,
@@ -1139,7 +1139,8 @@ __global__ __launch_bounds__(256) void preprocess_frames_kernel(
     const int t = (int)(i / ((long long)Wp * Hp));
     float c[3] = {0.f, 0.f, 0.f};
     if (x < Wn && y < Hn) {
-      float fx = (float)(((double)x + 0.5) * scx - 0.5), fy = (float)(((double)y + 0.5) * scy - 0.5);
+      const int xs = flip ? Wn - 1 - x : x;   // flip: the value the un-flipped output has at the mirrored column
+      float fx = (float)(((double)xs + 0.5) * scx - 0.5), fy = (float)(((double)y + 0.5) * scy - 0.5);
       int x0 = (int)floorf(fx), y0 = (int)floorf(fy);
       fx = fx - (float)x0;
       fy = fy - (float)y0;
@@ -1996,9 +1997,9 @@ int pave_ms_deform_attn_backward_f64(const double* value, const int64_t* spatial
                                     bs, S, M, D, L, Lq, P, im2col_step, stream);
 }
 
-int pave_preprocess_frames(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
-                           int Hn, int Wn, int Hp, int Wp, const float* mean, const float* std,
-                           int to_rgb, void* stream) {
+static int preprocess_frames_impl(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
+                                  int Hn, int Wn, int Hp, int Wp, const float* mean, const float* std,
+                                  int to_rgb, int flip, void* stream) {
   if (!src || !dst || !mean || !std) return fail(PAVE_E_ARG, "preprocess_frames: null pointer");
   if (T <= 0 || H0 <= 0 || W0 <= 0 || Hn <= 0 || Wn <= 0 || Hp < Hn || Wp < Wn)
     return fail(PAVE_E_ARG, "preprocess_frames: bad sizes");
@@ -2011,14 +2012,26 @@ int pave_preprocess_frames(const void* src, int src_is_u8, float* dst, int T, in
   if (src_is_u8)
     hipLaunchKernelGGL((preprocess_frames_kernel<unsigned char>), dim3((unsigned)nb), dim3(256), 0,
                        st, static_cast<const unsigned char*>(src), dst, T, H0, W0, Hn, Wn, Hp, Wp,
-                       mean[0], mean[1], mean[2], s0, s1, s2, to_rgb);
+                       mean[0], mean[1], mean[2], s0, s1, s2, to_rgb, flip);
   else
     hipLaunchKernelGGL((preprocess_frames_kernel<float>), dim3((unsigned)nb), dim3(256), 0, st,
                        static_cast<const float*>(src), dst, T, H0, W0, Hn, Wn, Hp, Wp, mean[0],
-                       mean[1], mean[2], s0, s1, s2, to_rgb);
+                       mean[1], mean[2], s0, s1, s2, to_rgb, flip);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
   return PAVE_OK;
+}
+
+int pave_preprocess_frames(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
+                           int Hn, int Wn, int Hp, int Wp, const float* mean, const float* std,
+                           int to_rgb, void* stream) {
+  return preprocess_frames_impl(src, src_is_u8, dst, T, H0, W0, Hn, Wn, Hp, Wp, mean, std, to_rgb, 0, stream);
+}
+
+int pave_preprocess_frames_flip(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
+                                int Hn, int Wn, int Hp, int Wp, const float* mean, const float* std,
+                                int to_rgb, void* stream) {
+  return preprocess_frames_impl(src, src_is_u8, dst, T, H0, W0, Hn, Wn, Hp, Wp, mean, std, to_rgb, 1, stream);
 }
 
 int pave_conv3x3_nhwc_f32(const float* x, const float* w, const float* bias, float* y, int N,

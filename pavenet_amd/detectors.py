@@ -5,6 +5,11 @@ opera/models/detectors/videoposev1.py:18-190 and mmdet SingleStageDetector.extra
 Native additions: ``forward_device`` keeps the whole clip batch on the device and returns
 fixed-shape result tensors (no host sync); B >= 1 clips per call (the reference asserts B = 1,
 videoposev1.py:175-177).
+
+Test-time augmentation (videoposev1.py:192-261, petr.py:118-187): ``aug_test`` / ``aug_test_device`` run one
+``forward_device`` per augmentation and merge the results with box NMS in one launch (``ops.aug_merge_nms``);
+``forward`` dispatches an augmentation list of more than one entry to ``aug_test`` as mmdet's
+``BaseDetector.forward_test`` does.
 """
 import numpy as np
 import torch
@@ -57,6 +62,10 @@ class VideoPoseV1(BaseModule):
             x = self.neck(x)
         return x
 
+    def extract_feats(self, imgs):
+        """mmdet BaseDetector.extract_feats: one feature pyramid per augmentation."""
+        return [self.extract_feat(img) for img in imgs]
+
     @torch.no_grad()
     def forward_device(self, img, img_metas, rescale=False, force_score_topk=None, strict=False,
                        **head_kwargs):
@@ -100,9 +109,76 @@ class VideoPoseV1(BaseModule):
         results_list = self.bbox_head.results_to_list(res)
         return [bbox_kpt2result(b, l, k, self.bbox_head.num_classes) for b, l, k in results_list]
 
+    def _tta_cfg(self):
+        cfg = self.test_cfg if self.test_cfg is not None else {}
+        missing = [k for k in ('nms', 'score_thr', 'max_per_img') if cfg.get(k) is None]
+        if missing:
+            raise ValueError(f'test-time augmentation needs test_cfg.{missing[0]} (missing: {", ".join(missing)}); '
+                             "the reference's flip-test config sets score_thr=0.0, max_per_img=100, "
+                             "nms=dict(type='soft_nms', iou_thr=0.5)")
+        return cfg
+
+    @torch.no_grad()
+    def aug_test_device(self, imgs, img_metas, strict=False, force_topk_proposals=None, force_score_topk=None):
+        """imgs / img_metas: one entry per augmentation (mmdet's nesting: img_metas[a] is the list of per-image
+        metas), every augmentation with the same B >= 1 images -> fixed-shape device dict: bboxes [B, M, 5]
+        (soft-NMS decayed scores), labels [B, M], kpts [B, M, K, 3] (score channel 1), keep [B, M] int32,
+        inds [B, M] (rows of the concatenated per-augmentation results), count [B]; results in original-image
+        pixels.  force_*: one entry (or None) per augmentation, passed to that augmentation's forward_device.
+
+        strict=True: each augmentation's forward runs strict (forward_device), and the merge runs under a census
+        too (``self.last_merge_census``): it must issue no ATen launch and no host sync."""
+        from . import ops
+        from .keypoints import flip_permutation
+        from .tta import aug_meta, parse_nms_cfg
+        A = len(imgs)
+        if A == 0 or len(img_metas) != A:
+            raise ValueError('aug_test: one img_metas entry per augmentation')
+        cfg = self._tta_cfg()
+        method, iou_thr, sigma, min_score, offset = parse_nms_cfg(cfg['nms'])
+        perm = flip_permutation(self.bbox_head.num_keypoints)
+        metas = [aug_meta(m) for m in img_metas]
+        fp = force_topk_proposals if force_topk_proposals is not None else [None] * A
+        fs = force_score_topk if force_score_topk is not None else [None] * A
+        results = []
+        for a in range(A):
+            kw = {} if fp[a] is None else dict(force_topk_proposals=fp[a])
+            results.append(self.forward_device(imgs[a], img_metas[a], rescale=False, force_score_topk=fs[a],
+                                               strict=strict, **kw))
+
+        def merge():
+            return ops.aug_merge_nms([r['bboxes'] for r in results], [r['kpts'] for r in results],
+                                     [r['keep'] for r in results], [m[0] for m in metas], [m[1] for m in metas],
+                                     [m[2] for m in metas], perm, score_thr=float(cfg['score_thr']),
+                                     max_num=int(cfg['max_per_img']), method=method, iou_thr=iou_thr,
+                                     sigma=sigma, min_score=min_score, offset=offset)
+        if not strict:
+            m = merge()
+        else:
+            from .census import FallbackError, LaunchCensus
+            with LaunchCensus() as census:
+                m = merge()
+            self.last_merge_census = census
+            s = census.summary()
+            if s['fallback_ops'] or s['aten_launches'] or s['host_syncs']:
+                raise FallbackError(f'{type(self).__name__}.aug_test_device(strict=True): the merge ran ATen '
+                                    f'operators on the device: {s}')
+        return dict(bboxes=m['dets'], labels=m['labels'], kpts=m['kpts'], keep=m['keep'], inds=m['inds'],
+                    count=m['count'])
+
+    @torch.no_grad()
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """videoposev1.py:225-261 / petr.py:151-187 -> per image (bbox_results, kpt_results); results are in
+        original-image pixels whatever `rescale` says, as in the reference."""
+        res = self.aug_test_device(imgs, img_metas)
+        results_list = self.bbox_head.results_to_list(res)
+        return [bbox_kpt2result(b, l, k, self.bbox_head.num_classes) for b, l, k in results_list]
+
     def forward(self, img, img_metas, return_loss=False, rescale=False, **kwargs):
         if return_loss:
             raise NotImplementedError('pavenet_amd is a forward (inference) path')
         if isinstance(img, (list, tuple)):  # mmdet forward_test nests one level per augmentation
+            if len(img) > 1:   # mmdet BaseDetector.forward_test (base.py:114-156): several augmentations
+                return self.aug_test(list(img), list(img_metas), rescale=rescale)
             img, img_metas = img[0], img_metas[0]
         return self.simple_test(img, img_metas, rescale=rescale)

@@ -70,6 +70,10 @@ SIGNATURES = {
     'pave_gather_rows_add_f32': [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp] + [_c_int] * 4 + [_vp],
     'pave_proposal_refs_f32': [_vp, _c_int, _vp, ctypes.c_longlong, _vp, _vp] + [_c_int] * 5 + [_vp],
     'pave_oks_nms_f32': [_vp] * 3 + [ctypes.c_double] + [_vp] * 2 + [_c_int] * 3 + [_vp],
+    'pave_preprocess_frames_flip': [_vp, _c_int, _vp] + [_c_int] * 7 + [_vp, _vp, _c_int, _vp],
+    'pave_aug_merge_nms_f32': [_vp, ctypes.c_float, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                               _c_int] + [_vp] * 7,
+    'pave_hflip_canvas_f32': [_vp, _vp, _vp] + [_c_int] * 5 + [_vp],
 }
 # every symbol include/pave_hip.h declares
 EXPORTED = tuple(SIGNATURES) + ('pave_abi_version', 'pave_last_error', 'pave_conv3x3_splitk_workspace_bytes',
@@ -84,8 +88,20 @@ class GnLevel(ctypes.Structure):
                 ('eps', ctypes.c_float)]
 
 
+AUG_MAX_AUGS, AUG_MAX_SLOTS, AUG_MAX_K = 16, 128, 64
+
+
+class AugPlan(ctypes.Structure):
+    """`pave_aug_plan` of include/pave_hip.h (the by-value argument of pave_aug_merge_nms_f32)."""
+    _fields_ = [('bboxes', ctypes.c_void_p * AUG_MAX_AUGS), ('kpts', ctypes.c_void_p * AUG_MAX_AUGS),
+                ('keep', ctypes.c_void_p * AUG_MAX_AUGS), ('flip', ctypes.c_int32 * AUG_MAX_AUGS),
+                ('img_w', ctypes.c_float * AUG_MAX_SLOTS), ('scale_factor', (ctypes.c_float * 4) * AUG_MAX_SLOTS),
+                ('flip_perm', ctypes.c_int32 * AUG_MAX_K), ('n_aug', ctypes.c_int32), ('B', ctypes.c_int32),
+                ('N', ctypes.c_int32), ('K', ctypes.c_int32)]
+
+
 _lib = None
-ABI_VERSION = 20  # == PAVE_ABI_VERSION of include/pave_hip.h this file's SIGNATURES were written for
+ABI_VERSION = 21  # == PAVE_ABI_VERSION of include/pave_hip.h this file's SIGNATURES were written for
 
 
 class NativeLibraryError(RuntimeError):

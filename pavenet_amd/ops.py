@@ -355,6 +355,103 @@ def oks_nms(kpts, scores, sigmas, thresh):
     return keep, order
 
 
+NMS_METHODS = {'nms': 0, 'naive': 1, 'linear': 2, 'gaussian': 3}   # include/pave_hip.h pave_aug_merge_nms_f32
+
+
+def aug_merge_nms(bboxes, kpts, keeps, flips, img_w, scale_factor, flip_perm, *, score_thr, max_num,
+                  method='linear', iou_thr=0.5, sigma=0.5, min_score=1e-3, offset=0):
+    """Test-time augmentation merge + box NMS in one launch (pave_aug_merge_nms_f32).
+
+    bboxes / kpts / keeps: one entry per augmentation -- [B, N, 5], [B, N, K, 3] fp32 and [B, N] int32 (or None:
+    every row enters); flips [A] bools; img_w [A][B] and scale_factor [A][B][4] host numbers; flip_perm [K] ints.
+    method: 'nms' (hard) or the soft-NMS kinds 'naive' / 'linear' / 'gaussian'.
+    -> dict(dets [B, M, 5], labels [B, M] int64, kpts [B, M, K, 3], inds [B, M] int64, keep [B, M] int32,
+    count [B] int32), M = min(max_num, A N) (A N when max_num <= 0); rows past count[b] have keep 0 and inds -1."""
+    lib = native.load()
+    A = len(bboxes)
+    _require(0 < A <= native.AUG_MAX_AUGS, f'aug_merge_nms: 1 .. {native.AUG_MAX_AUGS} augmentations, got {A}')
+    _require(len(kpts) == A and len(keeps) == A and len(flips) == A and len(img_w) == A and
+             len(scale_factor) == A, 'aug_merge_nms: one bboxes / kpts / keep / flip / img_w / scale_factor '
+             'entry per augmentation')
+    _require(method in NMS_METHODS, f'aug_merge_nms: method must be one of {sorted(NMS_METHODS)}, got {method!r}')
+    _require(int(offset) in (0, 1), 'aug_merge_nms: offset 0 or 1')
+    for a in range(A):
+        _dev(bboxes[a], f'bboxes[{a}]', torch.float32)
+        _dev(kpts[a], f'kpts[{a}]', torch.float32)
+        if keeps[a] is not None:
+            _dev(keeps[a], f'keep[{a}]', torch.int32)
+    B, N = bboxes[0].shape[:2]
+    K = kpts[0].shape[2]
+    dev = bboxes[0].device
+    for a in range(A):
+        _require(tuple(bboxes[a].shape) == (B, N, 5) and tuple(kpts[a].shape) == (B, N, K, 3),
+                 'aug_merge_nms: every augmentation needs bboxes [B, N, 5] and kpts [B, N, K, 3] of one shape')
+        _require(keeps[a] is None or tuple(keeps[a].shape) == (B, N), 'aug_merge_nms: keep must be [B, N]')
+        _require(bboxes[a].device == dev and kpts[a].device == dev and (keeps[a] is None or keeps[a].device == dev),
+                 'aug_merge_nms: all inputs on one device')
+        _require(len(img_w[a]) == B and len(scale_factor[a]) == B, 'aug_merge_nms: img_w / scale_factor [A][B]')
+    _require(A * B <= native.AUG_MAX_SLOTS, f'aug_merge_nms: at most {native.AUG_MAX_SLOTS} (augmentation, image) '
+             'pairs per launch')
+    _require(A * N <= 4096, f'aug_merge_nms: {A} x {N} = {A * N} boxes per image; the kernel keeps at most 4096 '
+             'in LDS')
+    _require(K <= native.AUG_MAX_K and len(flip_perm) == K and sorted(int(v) for v in flip_perm) == list(range(K)),
+             f'aug_merge_nms: flip_perm must be a permutation of range(K), K <= {native.AUG_MAX_K}')
+    plan = native.AugPlan()
+    for a in range(A):
+        plan.bboxes[a] = bboxes[a].data_ptr()
+        plan.kpts[a] = kpts[a].data_ptr()
+        plan.keep[a] = keeps[a].data_ptr() if keeps[a] is not None else None
+        plan.flip[a] = int(bool(flips[a]))
+        for b in range(B):
+            plan.img_w[a * B + b] = float(img_w[a][b])
+            sf = [float(v) for v in scale_factor[a][b]]
+            _require(len(sf) == 4, 'aug_merge_nms: scale_factor entries have 4 values')
+            for i in range(4):
+                plan.scale_factor[a * B + b][i] = sf[i]
+    for k in range(K):
+        plan.flip_perm[k] = int(flip_perm[k])
+    plan.n_aug, plan.B, plan.N, plan.K = A, B, N, K
+    total = A * N
+    M = min(int(max_num), total) if int(max_num) > 0 else total
+    dets = torch.empty((B, M, 5), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, M), dtype=torch.int64, device=dev)
+    out_k = torch.empty((B, M, K, 3), dtype=torch.float32, device=dev)
+    inds = torch.empty((B, M), dtype=torch.int64, device=dev)
+    keep = torch.empty((B, M), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = lib.pave_aug_merge_nms_f32(ctypes.byref(plan), float(score_thr), int(max_num), NMS_METHODS[method],
+                                        float(iou_thr), float(sigma), float(min_score), int(offset),
+                                        dets.data_ptr(), labels.data_ptr(), out_k.data_ptr(), inds.data_ptr(),
+                                        keep.data_ptr(), count.data_ptr(), _stream_ptr())
+    native.check(st, 'aug_merge_nms')
+    return dict(dets=dets, labels=labels, kpts=out_k, inds=inds, keep=keep, count=count)
+
+
+def hflip_canvas(x, valid_w):
+    """Horizontal flip of preprocessed canvases x [n, C, Hp, Wp] fp32 (pave_hflip_canvas_f32), out of place:
+    columns [0, w) of image i mirrored within themselves, w = valid_w (an int for all images, or a device int32
+    tensor [n]); the padding columns from w on are copied unchanged."""
+    lib = native.load()
+    _dev(x, 'x', torch.float32)
+    _require(x.dim() == 4, 'hflip_canvas: x must be [n, C, Hp, Wp]')
+    n, C, Hp, Wp = x.shape
+    if isinstance(valid_w, torch.Tensor):
+        _dev(valid_w, 'valid_w', torch.int32)
+        _require(valid_w.numel() == n and valid_w.device == x.device, 'hflip_canvas: valid_w [n] on x\'s device')
+        w_ptr, w_all = valid_w.data_ptr(), 0
+    else:
+        _require(0 <= int(valid_w) <= Wp, 'hflip_canvas: 0 <= valid_w <= Wp')
+        w_ptr, w_all = None, int(valid_w)
+    y = torch.empty_like(x)
+    if x.numel() == 0:
+        return y
+    with torch.cuda.device(x.device):
+        st = lib.pave_hflip_canvas_f32(x.data_ptr(), y.data_ptr(), w_ptr, w_all, n, C, Hp, Wp, _stream_ptr())
+    native.check(st, 'hflip_canvas')
+    return y
+
+
 def fuse_sum_nhwc(terms, relu=True):
     """HRNet fuse layer in one pass (pave_fuse_sum_nhwc_f32): terms = [(map, shift), ...] (1..4), map
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones

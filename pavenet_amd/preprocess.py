@@ -39,9 +39,12 @@ def plan_clip(H0, W0, img_scale=(1333, 800), size_divisor=1):
 
 
 def preprocess_clip(frames, img_scale=(1333, 800), size_divisor=1, mean=MEAN, std=STD,
-                    to_rgb=True):
+                    to_rgb=True, flip=False):
     """frames [T, H0, W0, 3] uint8 / float32 BGR on the device -> (img [1, T, 3, Hp, Wp] fp32,
-    img_meta dict with ori_shape / img_shape / pad_shape / batch_input_shape / scale_factor)."""
+    img_meta dict with ori_shape / img_shape / pad_shape / batch_input_shape / scale_factor / flip).
+
+    flip=True: mmdet's RandomFlip(horizontal) between Resize and Normalize -- the resized image is mirrored
+    within its Wn columns (pave_preprocess_frames_flip), the padding stays on the right."""
     lib = native.load()
     _require(frames.is_cuda and frames.dim() == 4 and frames.shape[-1] == 3 and
              frames.is_contiguous(), 'preprocess_clip: frames must be a contiguous device '
@@ -53,12 +56,71 @@ def preprocess_clip(frames, img_scale=(1333, 800), size_divisor=1, mean=MEAN, st
     m = (ctypes.c_float * 3)(*mean)
     s = (ctypes.c_float * 3)(*std)
     with torch.cuda.device(frames.device):
-        st = lib.pave_preprocess_frames(frames.data_ptr(), int(frames.dtype == torch.uint8),
-                                        out.data_ptr(), T, H0, W0, Hn, Wn, Hp, Wp,
-                                        ctypes.cast(m, ctypes.c_void_p),
-                                        ctypes.cast(s, ctypes.c_void_p), int(bool(to_rgb)),
-                                        _stream_ptr())
+        fn = lib.pave_preprocess_frames_flip if flip else lib.pave_preprocess_frames
+        st = fn(frames.data_ptr(), int(frames.dtype == torch.uint8), out.data_ptr(), T, H0, W0, Hn, Wn, Hp, Wp,
+                ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), int(bool(to_rgb)),
+                _stream_ptr())
     native.check(st, 'preprocess_frames')
     meta = dict(ori_shape=(H0, W0, 3), img_shape=(Hn, Wn, 3), pad_shape=(Hp, Wp, 3),
-                batch_input_shape=(Hp, Wp), scale_factor=scale_factor, flip=False)
+                batch_input_shape=(Hp, Wp), scale_factor=scale_factor, flip=bool(flip),
+                flip_direction='horizontal' if flip else None)
     return out, meta
+
+
+def aug_plan(img_scale, flip=False, flip_direction='horizontal'):
+    """mmdet MultiScaleFlipAug's order (mmdet/datasets/pipelines/test_time_aug.py:54-110): scales outer, flips
+    inner, [(False, None)] + [(True, d) for d in flip_direction] -> [(scale, flip, direction), ...]."""
+    scales = list(img_scale) if isinstance(img_scale, list) else [img_scale]
+    dirs = list(flip_direction) if isinstance(flip_direction, list) else [flip_direction]
+    flips = [(False, None)] + ([(True, d) for d in dirs] if flip else [])
+    return [(tuple(s), f, d) for s in scales for f, d in flips]
+
+
+def multi_scale_flip_aug(frames, img_scale=(1333, 800), flip=False, flip_direction='horizontal', size_divisor=1,
+                         mean=MEAN, std=STD, to_rgb=True):
+    """Every augmentation of MultiScaleFlipAug on the device -> (imgs, img_metas), one entry per augmentation in
+    mmdet's order: imgs[a] [1, T, 3, Hp, Wp] (a PETR image is imgs[a][:, 0]), img_metas[a] = [meta] (mmdet's
+    nesting: one list of per-image metas per augmentation).  Horizontal flips only, as the reference's
+    kpt_flip asserts."""
+    imgs, metas = [], []
+    for scale, f, d in aug_plan(img_scale, flip, flip_direction):
+        if f and d != 'horizontal':
+            raise NotImplementedError(f'flip_direction {d!r}: the reference flips key points horizontally only '
+                                      '(opera/core/keypoint/transforms.py:171)')
+        img, meta = preprocess_clip(frames, scale, size_divisor, mean, std, to_rgb, flip=f)
+        imgs.append(img)
+        metas.append([meta])
+    return imgs, metas
+
+
+def tta_from_config(cfg):
+    """The MultiScaleFlipAug arguments of a loaded config's ``data.test.pipeline`` -> kwargs of
+    ``multi_scale_flip_aug`` (img_scale, flip, flip_direction, size_divisor, mean, std, to_rgb).  Supports the
+    img_scale form; scale_factor raises NotImplementedError."""
+    data = cfg['data'] if 'data' in cfg else {}
+    pipeline = data.get('test', {}).get('pipeline')
+    if pipeline is None:
+        raise KeyError('config has no data.test.pipeline')
+    step = next((t for t in pipeline if str(t.get('type', '')).split('.')[-1] == 'MultiScaleFlipAug'), None)
+    if step is None:
+        raise ValueError('data.test.pipeline has no MultiScaleFlipAug step')
+    if step.get('scale_factor') is not None:
+        raise NotImplementedError('MultiScaleFlipAug(scale_factor=...) is not supported: use img_scale')
+    img_scale = step.get('img_scale')
+    if img_scale is None:
+        raise ValueError('MultiScaleFlipAug needs img_scale')
+    multi = isinstance(img_scale, list) and not isinstance(img_scale[0], (int, float))   # (a JSON pair is a list)
+    out = dict(img_scale=[tuple(s) for s in img_scale] if multi else tuple(img_scale),
+               flip=bool(step.get('flip', False)), flip_direction=step.get('flip_direction', 'horizontal'),
+               size_divisor=1, mean=MEAN, std=STD, to_rgb=True)
+    for t in step.get('transforms', []):
+        kind = str(t.get('type', '')).split('.')[-1]
+        if kind == 'Resize' and not t.get('keep_ratio', True):
+            raise NotImplementedError('Resize(keep_ratio=False) is not supported')
+        if kind == 'Normalize':
+            out.update(mean=tuple(t['mean']), std=tuple(t['std']), to_rgb=bool(t.get('to_rgb', True)))
+        if kind == 'Pad':
+            if t.get('size') is not None:
+                raise NotImplementedError('Pad(size=...) is not supported: use size_divisor')
+            out['size_divisor'] = int(t.get('size_divisor') or 1)
+    return out
