@@ -563,6 +563,46 @@ int pave_gemm_bf16x3_splitk_f32(const float* a, const void* w_planes, const floa
                                 long long workspace_bytes, void* stream);
 
 /*
+ * Form policy (per host thread): which kernel forms the GEMM / convolution dispatchers of this thread may pick.
+ * Several of them choose a form by the row count M -- split-K parts of the 3x3, strided 1x1 and long-K row GEMMs,
+ * the K-split small-row form, the LayerNorm pass instead of the fused LayerNorm epilogue -- and M comes from the
+ * batch, so a clip's last bits depended on what shared its batch.
+ *   0  today's selection, by row / tile count (the default);
+ *   1  "tile order": only forms bit-identical to the 128-row tile kernels (small-row one-wave, narrow, wide,
+ *      8-wave, two row tiles per wave); no split-K parts, no K-split small-row form, the fused LayerNorm epilogue
+ *      in its wide form (gemm_w_ln_kernel) at every M;
+ *   2  "K-split order": gemm_sk_kernel's order at every M for the plain row GEMM / LayerNorm GEMM where it
+ *      applies (K >= 512, or K >= 256 with N <= 512; the LayerNorm GEMM then takes its separate pass), order 1
+ *      everywhere else.
+ * Under 1 and 2 every decision is a function of (K, N, planes, kind, policy) only: an output row is a function of
+ * its own input row, whatever the batch.  pave_set_form_policy: PAVE_E_ARG outside 0 .. 2.
+ */
+int pave_set_form_policy(int policy);
+int pave_get_form_policy(void);
+
+/*
+ * The summation order a launch takes, as the dispatchers decide it (a pure host function: no device, no state but
+ * the diag build's form override).  kind: PAVE_FORM_*; K = the GEMM's reduction length (9 Cin for the 3x3, Cin
+ * for the strided 1x1), N = its output columns (padded as the entries pad them); nplanes 3 or PAVE_PLANES_FP16.
+ *   *order: PAVE_ORDER_*; it names the order, not the kernel -- forms proven bit-identical share one;
+ *   *ksplit: the split-K parts of PAVE_ORDER_SPLITK (their count changes the order), else 1.
+ */
+#define PAVE_FORM_ROWS 0          /* pave_gemm_bf16x3_f32, _ex (one output, no a_bias), _grouped */
+#define PAVE_FORM_ROWS_SPLITK 1   /* the same launch where a caller takes pave_gemm_bf16x3_splitk_f32 when it has a plan */
+#define PAVE_FORM_ROWS_TILE 2     /* a_bias, two outputs or two A sources (_ex, _cat): tile forms at every M */
+#define PAVE_FORM_LN 3            /* pave_gemm_bf16x3_ln_f32 */
+#define PAVE_FORM_CONV3X3 4       /* pave_conv3x3_split_f32 / pave_conv3x3_splitk_f32 */
+#define PAVE_FORM_CONV1X1S 5      /* pave_conv1x1_strided_split_f32 */
+#define PAVE_FORM_ENCPROJ 6       /* pave_gemm_bf16x3_encproj_f32 */
+#define PAVE_ORDER_TILE 0         /* the 128-row tile kernels' order (LN: the wide form's fused LayerNorm epilogue) */
+#define PAVE_ORDER_KSPLIT 1       /* gemm_sk_kernel's: K quarters over four waves, added ((p0 + p1) + p2) + p3 */
+#define PAVE_ORDER_SPLITK 2       /* split-K parts (*ksplit of them), added in order by a second launch */
+#define PAVE_ORDER_TILE_LNPASS 3  /* LN: tile-order GEMM, then the separate LayerNorm pass */
+#define PAVE_ORDER_KSPLIT_LNPASS 4 /* LN: K-split-order GEMM, then the separate LayerNorm pass */
+#define PAVE_ORDER_TILE_LN8 5     /* LN: the 8-wave block's fused LayerNorm (row statistics summed across 8 waves) */
+int pave_form_plan(long long M, int K, int N, int kind, int nplanes, int policy, int* order, int* ksplit);
+
+/*
  * ResNet Bottleneck of the 64-channel stage from its 3x3 convolution on, CHAINED with the next
  * block's conv1, in ONE launch (third_party/mmdetection/mmdet/models/backbones/resnet.py:263-300
  * Bottleneck.forward: conv2 + bn2 + relu -> conv3 + bn3 -> + identity | downsample(x) -> relu; then

@@ -512,6 +512,63 @@ def set_deterministic(model, flag=True):
     return model
 
 
+def set_batch_invariant(model, flag=True):
+    """Batch-invariant inference: every output of a clip is a function of that clip's input and canvas
+    (batch_input_shape) only, bit for bit -- whatever shares its batch, the batch size, and streaming
+    (VideoPoseStream) or forward_device.  forward_device / simple_test / forward and VideoPoseStream's encode /
+    decode / infer_video then run under a form policy of the GEMM / convolution dispatchers (ops.form_policy):
+    pixel-row launches (backbone, neck, encoder) in tile order (1), the decoders' and heads' query-row Linears in
+    K-split order where it applies (2) -- the call site chooses, never the batch.  Readable as
+    `model.batch_invariant`.  Scope: VideoPoseV1 (R-50, HRNet-w48, Swin-L) in the default 'bf16x3' GEMM mode;
+    'native' (hipBLASLt picks its kernels by M) and the 16-bit modes (the operand planes are chosen by row count)
+    raise ValueError, PETR and frame-sharded forwards NotImplementedError.  The default (flag=False) is the
+    selection by row count, unchanged."""
+    from .detectors import VideoPoseV1
+    from .petr import PETR
+    if flag:
+        if not isinstance(model, VideoPoseV1) or isinstance(model, PETR):
+            raise NotImplementedError(f'set_batch_invariant: {type(model).__name__} is not covered (VideoPoseV1 '
+                                      'only: PETR runs ATen launches whose strategies may depend on the batch)')
+        if _GEMM['mode'] != 'bf16x3':
+            raise ValueError(f"set_batch_invariant: GEMM mode {_GEMM['mode']!r} chooses its kernels by row count; "
+                             "batch-invariant inference needs set_gemm_mode('bf16x3')")
+    model.batch_invariant = bool(flag)
+    return model
+
+
+def batch_invariant_scope(model):
+    """The form-policy block of a forward of `model`: policy 1 when set_batch_invariant is on, else nothing."""
+    import contextlib
+    if not getattr(model, 'batch_invariant', False):
+        return contextlib.nullcontext()
+    if _GEMM['mode'] != 'bf16x3':
+        raise ValueError(f"batch-invariant forward under GEMM mode {_GEMM['mode']!r}: set_gemm_mode('bf16x3')")
+    from . import ops
+    return ops.form_policy(1)
+
+
+def query_rows_scope():
+    """Query-row launches (decoders, heads): form policy 2 inside a batch-invariant forward, else nothing."""
+    import contextlib
+    from . import ops
+    return ops.form_policy(2) if ops.current_form_policy() != 0 else contextlib.nullcontext()
+
+
+def fold_pos_ok(pb, n):
+    """May a positional term pb [n, Q, C] (batch first) be folded into a projection as ONE [Q, C] table?  A stride-0
+    expand always; a single clip / pose (n == 1) too -- except inside a batch-invariant forward, where only a
+    parameter-derived term folds, so that n == 1 and n > 1 evaluate the same expression."""
+    if pb.stride(0) == 0:
+        return True
+    if n != 1:
+        return False
+    from . import ops
+    if ops.current_form_policy() == 0:
+        return True
+    base = pb._base if pb._base is not None else pb
+    return isinstance(base, nn.Parameter)
+
+
 @MMCV_FEEDFORWARD_NETWORK.register_module()
 class FFN(BaseModule):
     """mmcv/cnn/bricks/transformer.py:1046-1120 (keys ``layers.0.0``, ``layers.1``)."""
@@ -634,7 +691,7 @@ class MultiheadAttention(BaseModule):
         if E != 256 or E // H != 32 or pos is None or post_norm is None or L > 568:
             return None
         pb = pos.transpose(0, 1)                      # [N, L, E]
-        if not (pb.stride(0) == 0 or N == 1) or pb.stride(2) != 1:
+        if not fold_pos_ok(pb, N) or pb.stride(2) != 1:
             return None                               # a per-sequence positional term
         pos_rows = pb[0]                              # [L, E] view of the embedding parameter
         base = pos_rows._base if pos_rows._base is not None else pos_rows

@@ -1747,6 +1747,130 @@ int launch_sk(const float* a, const uint16_t* w, const float* bias, const float*
   if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
   return PAVE_OK;
 }
+// ---------------------------------------------------------------------------
+// The K-split form with TN 32-column tiles per block (form policy 2 above kSkRows rows: the decoders' Linears of
+// a batch of 8 clips reach 2 400 rows).  gemm_sk_kernel re-reads a block's 32 A rows once per 32 output columns;
+// here the block owns 32 x (32 TN) outputs and wave w walks the same K quarter for all TN tiles, so the A slab it
+// loads feeds TN accumulators.  Every output element sees exactly gemm_sk_kernel's operations in its order: per
+// wave the slabs of its quarter in ascending order, per slab the six products o = 2, 1, 0 (pa = 0 .. o), the four
+// quarters added ((p0 + p1) + p2) + p3 through LDS, then bias, identity and activation -- the two forms are equal
+// bit for bit (tests/test_batch_invariant_gpu.py).  Tiles past N (wave-uniform) are skipped; the caller keeps
+// group_n % (32 TN) == 0 so that the TN tiles of a block read the same A columns.
+// ---------------------------------------------------------------------------
+template <int TN, int PF, int PL = 3>
+__global__ __launch_bounds__(256) void gemm_skm_kernel(
+    const float* __restrict__ A, const uint16_t* __restrict__ Wp, const float* __restrict__ bias,
+    const float* residual, float* out, const int M, const int K, const int N, const int relu,
+    const int lda, const int group_n, const int res_rows, const int n_real) {
+  __shared__ float part[4][16][64];                    // [wave][accumulator register][lane], one tile at a time
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lr = lane & 31, kh = lane >> 5;
+  const int ntn = (N + 32 * TN - 1) / (32 * TN);
+  const int tm = blockIdx.x / ntn, tn = blockIdx.x - tm * ntn;
+  const int m0 = tm * 32, n0 = tn * 32 * TN;
+  const int tiles = min(TN, (N - n0) / 32);           // N % 32 == 0: the block's real 32-column tiles
+  const int nslabs = K >> 4;
+  const int per = (nslabs + 3) >> 2;
+  const int sb = wave * per, se = min(nslabs, sb + per);
+  const int arow = min(m0 + lr, M - 1);
+  const float* ap = A + (long long)arow * lda + (group_n > 0 ? (n0 / group_n) * K : 0) + kh * 8;
+  const uint16_t* wp = Wp + ((long long)(n0 + lr) * 16 + kh * 8);
+  const long long w_plane = (long long)N * 16, w_slab = PL * w_plane;
+  f32x16 acc[TN];
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  f32x4 raw[PF][2];
+  u32x4 wf[PF][PL][TN];
+  auto load = [&](const int slab, const int set) {
+    raw[set][0] = *reinterpret_cast<const f32x4*>(ap + slab * 16);
+    raw[set][1] = *reinterpret_cast<const f32x4*>(ap + slab * 16 + 4);
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+      if (j < tiles)
+#pragma unroll
+        for (int p = 0; p < PL; ++p)
+          wf[set][p][j] = *reinterpret_cast<const u32x4*>(wp + slab * w_slab + p * w_plane + j * 32 * 16);
+  };
+#pragma unroll
+  for (int u = 0; u < PF; ++u)
+    if (sb + u < se) load(sb + u, u);
+  for (int s = sb; s < se; s += PF) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      if (s + u < se) {
+        u32x4 apl[PL];
+        if constexpr (PL == 1) {
+          apl[0] = u32x4{pack_rne_f16(raw[u][0].x, raw[u][0].y), pack_rne_f16(raw[u][0].z, raw[u][0].w),
+                         pack_rne_f16(raw[u][1].x, raw[u][1].y), pack_rne_f16(raw[u][1].z, raw[u][1].w)};
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            if (j < tiles)
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, apl[0]),
+                                                              __builtin_bit_cast(f16x8, wf[u][0][j]), acc[j], 0, 0, 0);
+        } else {
+          split8(raw[u][0], raw[u][1], apl);
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            if (j < tiles)
+#pragma unroll
+              for (int o = 2; o >= 0; --o)
+#pragma unroll
+                for (int pa = 0; pa <= o; ++pa)
+                  acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, apl[pa]),
+                                                                   __builtin_bit_cast(bf16x8, wf[u][o - pa][j]),
+                                                                   acc[j], 0, 0, 0);
+        }
+        if (s + u + PF < se) load(s + u + PF, u);
+      }
+    }
+  }
+  // ---- per tile: the four partial tiles meet in LDS, wave w finishes rows 8 w + (0 .. 3) + 4 kh (gemm_sk_kernel)
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    if (j >= tiles) break;                             // block-uniform
+    if (j > 0) __syncthreads();                        // the previous tile's reads are done
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[wave][r][lane] = acc[j][r];
+    __syncthreads();
+    const int col = n0 + j * 32 + lr;
+    const bool colok = col < n_real;
+    const float bj = (bias && colok) ? bias[col] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * wave + i;
+      const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+      float v = ((part[0][r][lane] + part[1][r][lane]) + part[2][r][lane]) + part[3][r][lane];
+      if (row < M && colok) {
+        v += bj;
+        if (residual) {
+          const int rr = res_rows > 0 ? (int)((unsigned)row % (unsigned)res_rows) : row;
+          v += residual[(long long)rr * n_real + col];
+        }
+        if (relu == 1) v = fmaxf(v, 0.f);
+        else if (relu == 2) v = gelu_erf(v);
+        else if (relu == 3) v = sigmoid_f(v);
+        out[(long long)row * n_real + col] = v;
+      }
+    }
+  }
+}
+
+constexpr int kSkmTiles = 4;   // 32-column tiles per block of the multi-tile K-split form
+template <int PL = 3>
+int launch_skm(const float* a, const uint16_t* w, const float* bias, const float* residual, float* out,
+               long long M, int K, int N, int relu, int lda, int group_n, int res_rows, int n_real,
+               hipStream_t st) {
+  const long long blocks = ((M + 31) / 32) * ((N + 32 * kSkmTiles - 1) / (32 * kSkmTiles));
+  if (blocks >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_skm: grid too large");
+  hipLaunchKernelGGL((gemm_skm_kernel<kSkmTiles, 2, PL>), dim3((unsigned)blocks), dim3(256), 0, st, a, w, bias,
+                     residual, out, (int)M, K, N, relu, lda, group_n, res_rows, n_real);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
+  return PAVE_OK;
+}
 // Taken from K = 512 on, up to kSkTiles blocks (tools/small_gemm_ksplit_ab.py, us per launch behind a busy stream,
 // K-split | one-wave form | tile kernels): at K = 256 a wave's whole walk is 16 slabs and the split only adds blocks
 // (1 200 x 256 x 2 688: 22 | 15 | 15), at K = 1 024 it is what the launch waits for (300 .. 1 200 x 1024 x 256:
@@ -1775,6 +1899,39 @@ inline bool small_rows_ksplit_form(long long M, int N, int K) {
 constexpr long long kSmallRows = 8192;
 inline bool small_rows_form(long long M, int N) {
   return M < kSmallRows && ((M + 127) / 128) * ((N + 127) / 128) < 64;
+}
+
+// Form policy 2 ("K-split order"): the (K, N) that take gemm_sk_kernel's order at every M -- where policy 0 takes
+// it for a few hundred rows: K >= 512 at any width, K = 256 .. 511 for the narrow outputs (wider ones at K = 256
+// are the tile kernels' ground already at 1 200 rows, tools/small_gemm_ksplit_ab.py).
+inline bool ksplit_order_applies(int K, int N) { return K >= 512 || (K >= 256 && N <= 512); }
+
+// The summation-order decisions of the dispatchers below, as functions of the launch and the form policy (shared
+// by the launch code and pave_form_plan).  Policy 0: today's selection, by row / tile count.  Policies 1 and 2:
+// by (K, N, kind) alone -- the forms that may still be picked by M (small-row one-wave, narrow / wide, 8-wave,
+// two row tiles per wave, the multi-tile K-split form) are bit-identical to the one the policy names.
+// Plain row GEMM (no a_bias, one output, no split-K parts): gemm_sk_kernel's order?
+inline bool rows_ksplit(long long M, int N, int K, int policy) {
+  if (policy == 0) return small_rows_ksplit_form(M, N, K);
+  return policy == 2 && ksplit_order_applies(K, N);
+}
+// LayerNorm-epilogue GEMM: GEMM + a LayerNorm pass (pave_bias_add_layernorm_f32) instead of the fused epilogue,
+// and the GEMM in gemm_sk_kernel's order.  The LayerNorm pass and the fused epilogue do not agree bit for bit
+// (another association of the row sums), so policies 1 and 2 never switch between them by M: 1 keeps the fused
+// epilogue, 2 the K-split GEMM + pass wherever its order applies.
+// The fused epilogue itself has two forms that do not agree bit for bit either: the wide one (gemm_w_ln_kernel, a
+// wave owns 32 whole rows) and the 8-wave block (gemm_q_ln_kernel, a row's statistics summed across its waves in
+// another order; tests/test_ops_gpu.py compares them at 4e-6).  Policy 0 takes the wide form from 512 row tiles on;
+// policies 1 and 2 take it at every M (in row chunks below its 4 GiB identity-buffer limit).
+inline void ln_form(long long M, int K, int N, int policy, int dv, bool* lnpass, bool* ksplit, bool* wide) {
+  if (policy == 0) {
+    *lnpass = small_rows_form(M, N) && (dv == 0 || dv == 19);
+    *ksplit = *lnpass && small_rows_ksplit_form(M, N, K) && dv == 0;
+    *wide = dv != 13 && ((M + QBM - 1) / QBM >= 512 || dv == 14) && M * 1024ll < (1ll << 32);
+  } else {
+    *lnpass = *ksplit = policy == 2 && ksplit_order_applies(K, N) && (dv == 0 || dv == 21);
+    *wide = true;
+  }
 }
 
 constexpr int W_SMEM = 2 * (QBM * 64 + 3 * 256 * 32);   // wide form: ring of 2 x 32 KiB
@@ -1820,10 +1977,15 @@ int launch_w(const float* a, const uint16_t* w, const float* bias, const float* 
 // Split-K plan of an [M, Kp] x [Np, Kp] product: how many parts the K axis is cut into (1 = none)
 // and the slabs per part.  Worth it when the tiles alone leave most of the 512 block slots of the
 // chip empty and K is very long; every part gets an even number >= 64 of slabs.
-void pave_internal_splitk_plan(long long M, int Kp, int Np, int* ksplit, int* ks_slabs) {
+// Form policies 1 and 2: never (the parts and their count change the summation order with the batch).
+static thread_local int t_form_policy = 0;
+int pave_internal_form_policy() { return t_form_policy; }
+
+static void splitk_plan(long long M, int Kp, int Np, int policy, int* ksplit, int* ks_slabs) {
   const long long tiles = ((M + QBM - 1) / QBM) * (Np % 256 == 0 ? Np / 256 : (Np + 127) / 128);
   const int nsl = Kp / 16;
   *ksplit = 1, *ks_slabs = 0;
+  if (policy != 0) return;
   // Few tiles and a very long K (K >= 8192: the ChannelMapper's 3x3 on C5): 8 parts.
   // WHAT THE PLAN DEPENDS ON: the K range and the TILE-COUNT CLASS of the launch (< 16, < 128, < 200 tiles), and
   // the tile count comes from the batch.  The summation order of an output is therefore a function of the batch
@@ -1847,6 +2009,56 @@ void pave_internal_splitk_plan(long long M, int Kp, int Np, int* ksplit, int* ks
   }
   if (parts < 2) return;
   *ksplit = parts, *ks_slabs = per;
+}
+void pave_internal_splitk_plan(long long M, int Kp, int Np, int* ksplit, int* ks_slabs) {
+  splitk_plan(M, Kp, Np, t_form_policy, ksplit, ks_slabs);
+}
+
+extern "C" int pave_set_form_policy(int policy) {
+  if (policy < 0 || policy > 2)
+    return pave_internal_fail(PAVE_E_ARG, "set_form_policy: 0 (by row count), 1 (tile order) or 2 (K-split order)");
+  t_form_policy = policy;
+  return PAVE_OK;
+}
+extern "C" int pave_get_form_policy(void) { return t_form_policy; }
+
+extern "C" int pave_form_plan(long long M, int K, int N, int kind, int nplanes, int policy, int* order,
+                              int* ksplit) {
+  if (!order || !ksplit || M <= 0 || K <= 0 || N <= 0 || policy < 0 || policy > 2 ||
+      (nplanes != 3 && nplanes != PAVE_PLANES_FP16) || kind < PAVE_FORM_ROWS || kind > PAVE_FORM_ENCPROJ)
+    return pave_internal_fail(PAVE_E_ARG, "form_plan: M, K, N > 0, a PAVE_FORM_* kind, policy 0 .. 2, nplanes 3 "
+                                          "or PAVE_PLANES_FP16");
+  // the sizes the entries hand the dispatchers: K padded to 32 columns, N to 64 rows of weight planes
+  const int Kp = (K + 31) / 32 * 32, Np = (N + 63) / 64 * 64;
+  const int dv = pave_internal_diag_variant();
+  *order = PAVE_ORDER_TILE, *ksplit = 1;
+  int parts = 1, per = 0;
+  switch (kind) {
+    case PAVE_FORM_ROWS_SPLITK:   // pave_gemm_bf16x3_splitk_f32 where pave_gemm_splitk_workspace_bytes > 0
+      if (dv != 9) splitk_plan(M, Kp, Np, policy, &parts, &per);
+      if (parts > 1) {
+        *order = PAVE_ORDER_SPLITK, *ksplit = parts;
+        break;
+      }
+      [[fallthrough]];
+    case PAVE_FORM_ROWS:
+      if (rows_ksplit(M, Np, Kp, policy) && (dv == 0 || dv == 21)) *order = PAVE_ORDER_KSPLIT;
+      break;
+    case PAVE_FORM_LN: {
+      bool lnpass, sk, wide;
+      ln_form(M, Kp, Np, policy, dv, &lnpass, &sk, &wide);
+      if (lnpass) *order = sk ? PAVE_ORDER_KSPLIT_LNPASS : PAVE_ORDER_TILE_LNPASS;
+      else *order = wide ? PAVE_ORDER_TILE : PAVE_ORDER_TILE_LN8;
+      break;
+    }
+    case PAVE_FORM_CONV3X3:
+      if (dv != 9) splitk_plan(M, Kp, Np, policy, &parts, &per);
+      if (parts > 1) *order = PAVE_ORDER_SPLITK, *ksplit = parts;
+      break;
+    default:   // PAVE_FORM_ROWS_TILE, PAVE_FORM_CONV1X1S, PAVE_FORM_ENCPROJ: the tile kernels at every M
+      break;
+  }
+  return PAVE_OK;
 }
 int pave_internal_splitk_reduce(const float* ws, int parts, long long M, int n, const float* bias,
                                 const float* residual, int relu, float* out, void* stream) {
@@ -1907,10 +2119,17 @@ static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_pl
   // ... and, from round 6 on, with the K axis split over the block's four waves wherever the launch is at most
   // kSkTiles 32 x 32 tiles, at ANY output width (diag variant 19: the forms as they were, for A/B and the tests
   // that compare the one-wave form with the tile kernels bit for bit)
-  if (kind == 0 && small_rows_ksplit_form(M, N, K) && !a_bias && !out2 && ksplit == 1 &&
-      pave_internal_diag_variant() == 0)
+  // (form policy 1: never; 2: wherever ksplit_order_applies(K, N), above kSkRows rows with kSkmTiles column tiles
+  // per block -- the same order; diag variant 21: gemm_sk_kernel there too)
+  const int dv0 = pave_internal_diag_variant();
+  if (kind == 0 && rows_ksplit(M, N, K, pave_internal_form_policy()) && !a_bias && !out2 && ksplit == 1 &&
+      (dv0 == 0 || dv0 == 21)) {
+    if (M > kSkRows && dv0 != 21 && (W <= 0 || W % (32 * kSkmTiles) == 0))
+      return launch_skm<PL>(a, w, bias, residual, out, M, K, N, relu, H > 0 ? H : K, W > 0 ? W : 0, os.res_rows,
+                            n_real, st);
     return launch_sk<PL>(a, w, bias, residual, out, M, K, N, relu, H > 0 ? H : K, W > 0 ? W : 0, os.res_rows,
                          n_real, st);
+  }
   if (kind == 0 && small_rows_form(M, N) && N <= 512 && !a_bias && !out2 && ksplit == 1 &&
       (pave_internal_diag_variant() == 0 || pave_internal_diag_variant() == 19))
     return launch_s<1, 4, PL>(a, w, bias, residual, out, M, K, N, relu, H > 0 ? H : K, W > 0 ? W : 0, os.res_rows,
@@ -2054,12 +2273,18 @@ static int gemm_q_ln_go(const float* a, const void* w_planes, const float* bias,
                         int K, int N, void* stream) {
   if (K % 32 != 0 || K < 64 || N != 256)
     return pave_internal_fail(PAVE_E_UNSUPPORTED, "gemm_q_ln: K %% 32 == 0, K >= 64 and N == 256 required");
-  if (small_rows_form(M, N) && (pave_internal_diag_variant() == 0 || pave_internal_diag_variant() == 19)) {
+  bool lnpass, sk, wide;
+  ln_form(M, K, N, pave_internal_form_policy(), pave_internal_diag_variant(), &lnpass, &sk, &wide);
+  if (lnpass) {
     // few rows: the small-row GEMM (bias + identity in its epilogue), then LayerNorm in place -- two
     // launches of a few microseconds instead of 10 row tiles walking K behind barriers
-    const int st1 = (small_rows_ksplit_form(M, N, K) && pave_internal_diag_variant() == 0)
-        ? launch_sk<PL>(a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, K, 0, 0, N,
-                        reinterpret_cast<hipStream_t>(stream))
+    // (form policy 2: at every M, the multi-tile K-split form above kSkRows rows)
+    const int st1 = sk
+        ? ((M > kSkRows && pave_internal_diag_variant() != 21)
+               ? launch_skm<PL>(a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, K, 0, 0,
+                                N, reinterpret_cast<hipStream_t>(stream))
+               : launch_sk<PL>(a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, K, 0, 0,
+                               N, reinterpret_cast<hipStream_t>(stream)))
         : launch_s<1, 4, PL>(a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, K,
                                    0, 0, N, reinterpret_cast<hipStream_t>(stream));
     if (st1 != PAVE_OK) return st1;
@@ -2079,10 +2304,11 @@ static int gemm_q_ln_go(const float* a, const void* w_planes, const float* bias,
   // From two tiles per CU slot on: the wide form (4 waves, a wave owns 32 whole rows; LayerNorm on the
   // accumulator layout, two blocks per CU) -- 602 -> 548 us at K = 256, 1 715 -> 1 606 us at K = 1024 for
   // 625 044 rows (tools/ln_ab.py).  Few tiles (the decoders' M = 1 200) keep the 8-wave block: twice the
-  // waves per tile.  (diag variant 13: always the 8-wave form, 14: always the wide form.)  The identity
-  // rows are read through a buffer resource: M * 1024 bytes < 4 GiB.
-  const int dvl = pave_internal_diag_variant();
-  if (dvl != 13 && (gx >= 512 || dvl == 14) && M * 1024ll < (1ll << 32)) {
+  // waves per tile.  (diag variant 13: always the 8-wave form, 14: always the wide form; form policies 1 / 2:
+  // always the wide form -- ln_form.)  The identity rows are read through a buffer resource: M * 1024 bytes
+  // < 4 GiB, so beyond 2^22 rows (policies 1 / 2 only) the launch goes in row chunks of whole 128-row tiles --
+  // a row's values do not depend on the tile it sits in.
+  if (wide) {
     static bool attr_w = false;
     if (!attr_w) {
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_w_ln_kernel<PL>),
@@ -2090,11 +2316,16 @@ static int gemm_q_ln_go(const float* a, const void* w_planes, const float* bias,
         return pave_internal_fail(PAVE_E_LAUNCH, "gemm_w_ln: cannot raise dynamic LDS limit");
       attr_w = true;
     }
-    hipLaunchKernelGGL(gemm_w_ln_kernel<PL>, dim3((unsigned)gx), dim3(256), w_smem<PL>(),
-                       reinterpret_cast<hipStream_t>(stream), a, static_cast<const uint16_t*>(w_planes),
-                       bias, residual, out, (int)M, K, N, QLn{gamma, beta, eps});
-    const hipError_t ew = hipGetLastError();
-    if (ew != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(ew));
+    constexpr long long kChunk = (1ll << 22) - QBM;
+    for (long long r0 = 0; r0 < M; r0 += kChunk) {
+      const long long m = M - r0 < kChunk ? M - r0 : kChunk;
+      hipLaunchKernelGGL(gemm_w_ln_kernel<PL>, dim3((unsigned)((m + QBM - 1) / QBM)), dim3(256), w_smem<PL>(),
+                         reinterpret_cast<hipStream_t>(stream), a + r0 * K, static_cast<const uint16_t*>(w_planes),
+                         bias, residual ? residual + r0 * N : nullptr, out + r0 * N, (int)m, K, N,
+                         QLn{gamma, beta, eps});
+      const hipError_t ew = hipGetLastError();
+      if (ew != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(ew));
+    }
     return PAVE_OK;
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), smem,

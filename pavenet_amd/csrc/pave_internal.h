@@ -11,6 +11,8 @@ int pave_internal_gemm_q(const float* a, const float* a_bias, const void* w_plan
 // (planes: 3 = the exact bf16 split, 1 = one plane of fp16 operands)
 // split-K (few output rows, long K): plan, and the ordered sum of the parts + bias / residual / ReLU
 void pave_internal_splitk_plan(long long M, int Kp, int Np, int* ksplit, int* ks_slabs);
+// the calling thread's form policy (pave_set_form_policy); pave_internal_splitk_plan honours it
+int pave_internal_form_policy();
 int pave_internal_splitk_reduce(const float* ws, int parts, long long M, int n, const float* bias,
                                 const float* residual, int relu, float* out, void* stream);
 int pave_internal_gemm_q_ln(const float* a, const void* w_planes, const float* bias, const float* residual,

@@ -84,14 +84,14 @@ def cat_proj_rows(mod, query, query_pos, frames=None):
     self-attention does the same with its q | k | v projection, bricks.MultiheadAttention).  The weight rows are
     zero-padded to N % 128 == 0 (the row stride of the result; the fused kernels take it as `proj_ld`).
     query, query_pos: sequence-first [Q, bs, C].  Returns proj [bs * Q, >= N]; anything else: the plain expression."""
-    from .bricks import fused_mode
+    from .bricks import fold_pos_ok, fused_mode
     q = batch_first(query)
     bs, Q, C = q.shape
     pos_rows = None
     if (FOLD_QUERY_POS and query_pos is not None and q.is_cuda and q.dtype == torch.float32 and fused_mode()
             and not torch.is_grad_enabled() and query_pos.shape == query.shape and C % 64 == 0 and q.is_contiguous()):
         pb = query_pos.transpose(0, 1)                       # [bs, Q, C]
-        if (pb.stride(0) == 0 or bs == 1) and pb.stride(2) == 1:
+        if fold_pos_ok(pb, bs) and pb.stride(2) == 1:
             pos_rows = pb[0]                                 # [Q, C] view of the embedding parameter
     if pos_rows is None:
         w, b = mod._cat_proj(frames)

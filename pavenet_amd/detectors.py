@@ -14,7 +14,7 @@ Test-time augmentation (videoposev1.py:192-261, petr.py:118-187): ``aug_test`` /
 import numpy as np
 import torch
 
-from .bricks import BaseModule
+from .bricks import BaseModule, batch_invariant_scope
 from .registry import DETECTORS, MMDET_MODELS
 
 
@@ -33,6 +33,9 @@ def bbox_kpt2result(bboxes, labels, kpts, num_classes):
 
 @DETECTORS.register_module()
 class VideoPoseV1(BaseModule):
+
+    # bricks.set_batch_invariant: every output of a clip a function of that clip's input and canvas only
+    batch_invariant = False
 
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None,
                  pretrained=None, init_cfg=None):
@@ -96,11 +99,14 @@ class VideoPoseV1(BaseModule):
             self.last_census = census
             census.raise_on_fallback(f'{type(self).__name__}.forward_device(strict=True)')
             return res
-        feat = self.extract_feat(img)
-        head_kwargs.setdefault('last_level_only', True)   # get_bboxes reads [-1] only
-        outs = self.bbox_head(feat, img_metas, **head_kwargs)
-        return self.bbox_head.get_bboxes(outs, img_metas, rescale=rescale,
-                                         force_score_topk=force_score_topk)
+        if self.batch_invariant and head_kwargs.get('frame_shard') is not None:
+            raise NotImplementedError('batch-invariant inference (set_batch_invariant) does not cover frame_shard=')
+        with batch_invariant_scope(self):
+            feat = self.extract_feat(img)
+            head_kwargs.setdefault('last_level_only', True)   # get_bboxes reads [-1] only
+            outs = self.bbox_head(feat, img_metas, **head_kwargs)
+            return self.bbox_head.get_bboxes(outs, img_metas, rescale=rescale,
+                                             force_score_topk=force_score_topk)
 
     @torch.no_grad()
     def simple_test(self, img, img_metas, rescale=False):

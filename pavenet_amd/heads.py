@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .bricks import (BaseModule, Linear, bias_init_with_prob, build_activation_layer,
-                     constant_init, mlp_rows)
+                     constant_init, mlp_rows, query_rows_scope)
 from .deform_attn import frame_prefixes
 from .transformer import _frame_branches, _ref_update
 from .registry import HEADS, LOSSES, MMDET_MODELS, build_positional_encoding, build_transformer
@@ -305,26 +305,27 @@ class VideoPoseHeadMulFrames(BaseModule):
         # losses (HEAD:1304-1330 reads [-1]); in eval mode they are skipped unless asked for.
         only_last = self.eval_last_level_only if last_level_only is None else bool(last_level_only)
         levels = [n_lvl - 1] if (only_last and not self.training) else range(n_lvl)
-        for lvl in levels:
-            reference = init_reference if lvl == 0 else inter_references[lvl - 1]
-            if lvl == n_lvl - 1:
-                # all T frames' key-point branches on hs[lvl] at once (one GEMM + batched GEMMs,
-                # transformer._frame_branches), then ONE reference update over [B, T*Q, 2K]
-                brs = [getattr(self, ('next_' if (T == 5 and t == 4) else fp) + 'kpt_branches')
-                       for t, fp in enumerate(self.frame_prefixes)]   # HEAD:503 quirk kept
-                poses = _frame_branches(brs, lvl, hs[lvl], 1, update_ref=reference)
-                all_frame_poses = poses
-                aux_poses = [None if t == c else poses[:, t * Q:(t + 1) * Q] for t in range(T)]
-                outputs_kpt = poses[:, c * Q:(c + 1) * Q]
-            else:
-                # (tmp + inverse_sigmoid(reference)).sigmoid(): one launch on the device
-                outputs_kpt = _ref_update(mlp_rows(self.kpt_branches[lvl], hs[lvl]),
-                                          reference[:, c * Q:(c + 1) * Q])
-            outputs_class = mlp_rows(self.cls_branches[lvl], hs[lvl])
-            output_sigma = mlp_rows(self.dec_fc_sigma_branches[lvl], hs[lvl], act='sigmoid')
-            outputs_classes.append(outputs_class)
-            outputs_kpts.append(outputs_kpt)
-            output_sigmas.append(output_sigma)
+        with query_rows_scope():   # (query rows: form policy 2 in a batch-invariant forward)
+            for lvl in levels:
+                reference = init_reference if lvl == 0 else inter_references[lvl - 1]
+                if lvl == n_lvl - 1:
+                    # all T frames' key-point branches on hs[lvl] at once (one GEMM + batched GEMMs,
+                    # transformer._frame_branches), then ONE reference update over [B, T*Q, 2K]
+                    brs = [getattr(self, ('next_' if (T == 5 and t == 4) else fp) + 'kpt_branches')
+                           for t, fp in enumerate(self.frame_prefixes)]   # HEAD:503 quirk kept
+                    poses = _frame_branches(brs, lvl, hs[lvl], 1, update_ref=reference)
+                    all_frame_poses = poses
+                    aux_poses = [None if t == c else poses[:, t * Q:(t + 1) * Q] for t in range(T)]
+                    outputs_kpt = poses[:, c * Q:(c + 1) * Q]
+                else:
+                    # (tmp + inverse_sigmoid(reference)).sigmoid(): one launch on the device
+                    outputs_kpt = _ref_update(mlp_rows(self.kpt_branches[lvl], hs[lvl]),
+                                              reference[:, c * Q:(c + 1) * Q])
+                outputs_class = mlp_rows(self.cls_branches[lvl], hs[lvl])
+                output_sigma = mlp_rows(self.dec_fc_sigma_branches[lvl], hs[lvl], act='sigmoid')
+                outputs_classes.append(outputs_class)
+                outputs_kpts.append(outputs_kpt)
+                output_sigmas.append(output_sigma)
         one = len(outputs_classes) == 1        # a one-level stack is a view, not a copy
         stack = (lambda ts: ts[0].unsqueeze(0)) if one else torch.stack
         # (the encoder-side predictions only feed training losses: left un-activated at inference)
@@ -368,16 +369,17 @@ class VideoPoseHeadMulFrames(BaseModule):
         only_last = self.eval_last_level_only if last_level_only is None else bool(last_level_only)
         lazy = only_last and not self.training
         levels = [n_lvl - 1] if lazy else range(n_lvl)
-        for lvl in levels:
-            reference = init_reference if lvl == 0 else inter_references[lvl - 1]
-            n = reference.shape[0] // T
-            h = hs[lvl] if hs[lvl].is_contiguous() else hs[lvl].contiguous()   # (one layout copy for both branches)
-            tmp_kpt = mlp_rows(self.refine_kpt_branches[lvl], h)
-            tmp_sigma = mlp_rows(self.refine_fc_sigma_branches[lvl], h, act='sigmoid')
-            if not lazy:    # (the refine score only feeds the training loss, HEAD:640-674: get_bboxes never reads it)
-                outs_score.append(torch.mean(1 - tmp_sigma, dim=2, keepdim=True))
-            outs_kpt.append(_ref_update(tmp_kpt, reference[c * n:(c + 1) * n]))
-            outs_sigma.append(tmp_sigma)
+        with query_rows_scope():
+            for lvl in levels:
+                reference = init_reference if lvl == 0 else inter_references[lvl - 1]
+                n = reference.shape[0] // T
+                h = hs[lvl] if hs[lvl].is_contiguous() else hs[lvl].contiguous()   # (one layout copy for both branches)
+                tmp_kpt = mlp_rows(self.refine_kpt_branches[lvl], h)
+                tmp_sigma = mlp_rows(self.refine_fc_sigma_branches[lvl], h, act='sigmoid')
+                if not lazy:    # (the refine score only feeds the training loss, HEAD:640-674: get_bboxes never reads it)
+                    outs_score.append(torch.mean(1 - tmp_sigma, dim=2, keepdim=True))
+                outs_kpt.append(_ref_update(tmp_kpt, reference[c * n:(c + 1) * n]))
+                outs_sigma.append(tmp_sigma)
         stack = (lambda ts: ts[0].unsqueeze(0)) if len(outs_kpt) == 1 else torch.stack
         return stack(outs_kpt), (None if lazy else stack(outs_score)), stack(outs_sigma), hs
 

@@ -74,10 +74,12 @@ SIGNATURES = {
     'pave_aug_merge_nms_f32': [_vp, ctypes.c_float, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                _c_int] + [_vp] * 7,
     'pave_hflip_canvas_f32': [_vp, _vp, _vp] + [_c_int] * 5 + [_vp],
+    'pave_set_form_policy': [_c_int],
+    'pave_form_plan': [ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
 }
 # every symbol include/pave_hip.h declares
 EXPORTED = tuple(SIGNATURES) + ('pave_abi_version', 'pave_last_error', 'pave_conv3x3_splitk_workspace_bytes',
-                                'pave_gemm_splitk_workspace_bytes')
+                                'pave_gemm_splitk_workspace_bytes', 'pave_get_form_policy')
 
 
 
@@ -115,6 +117,12 @@ def _open(path):
             f'g.build()"` (hipcc --offload-arch=gfx950). pavenet_amd has no '
             f'CPU or eager fallback for its HIP kernels.')
     lib = ctypes.CDLL(path)
+    # entry points added without a signature change keep the ABI version: a library built before them lacks them
+    missing = [n for n in EXPORTED if not hasattr(lib, n)]
+    if missing:
+        raise NativeLibraryError(
+            f'{path} lacks {", ".join(missing)} (built from older sources): rebuild it '
+            f'(`python -m pavenet_amd.build_native`)')
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
@@ -127,6 +135,8 @@ def _open(path):
     lib.pave_conv3x3_splitk_workspace_bytes.argtypes = [_c_int] * 6
     lib.pave_gemm_splitk_workspace_bytes.restype = ctypes.c_longlong
     lib.pave_gemm_splitk_workspace_bytes.argtypes = [ctypes.c_longlong, _c_int, _c_int]
+    lib.pave_get_form_policy.restype = _c_int
+    lib.pave_get_form_policy.argtypes = []
     have = lib.pave_abi_version()
     if have != ABI_VERSION:   # a stale .so called with the wrong argument list corrupts memory
         raise NativeLibraryError(

@@ -15,6 +15,7 @@ PyTorch is used here only for device memory and the current HIP stream.  There
 is no CPU path: a non-device tensor raises, exactly as the reference's
 ``AT_ASSERTM(value.is_cuda())`` does (ms_deform_attn_cuda.cu:221-230).
 """
+import contextlib
 import ctypes
 
 import torch
@@ -32,6 +33,45 @@ KERNEL_EVENT_SHAPES = None   # tools/gemm_census.py: a list that receives the sh
 
 def _stream_ptr():
     return torch.cuda.current_stream().cuda_stream
+
+
+# Form policy of the GEMM / convolution dispatchers (pave_set_form_policy, include/pave_hip.h): 0 = the selection
+# by row count, 1 = tile order, 2 = K-split order where it applies.  Under 1 and 2 an output row is a function of
+# its own input row only, whatever the batch (bricks.set_batch_invariant).
+FORM_ROWS, FORM_ROWS_SPLITK, FORM_ROWS_TILE, FORM_LN, FORM_CONV3X3, FORM_CONV1X1S, FORM_ENCPROJ = range(7)
+ORDER_TILE, ORDER_KSPLIT, ORDER_SPLITK, ORDER_TILE_LNPASS, ORDER_KSPLIT_LNPASS, ORDER_TILE_LN8 = range(6)
+
+
+def current_form_policy():
+    """The calling thread's form policy (the library keeps one per host thread: a batch-invariant forward on one
+    Python thread leaves another thread's default-mode forward alone)."""
+    return native.load().pave_get_form_policy()
+
+
+@contextlib.contextmanager
+def form_policy(p):
+    """Run the block's launches under form policy p (0 | 1 | 2) on the calling thread; the previous policy is back on
+    exit, on an exception too.  The policy is the library's at the time of entry: enter native.diag_build() first."""
+    _require(p in (0, 1, 2), 'form_policy: 0, 1 or 2')
+    lib = native.load()
+    prev = lib.pave_get_form_policy()
+    native.check(lib.pave_set_form_policy(int(p)), 'set_form_policy')
+    try:
+        yield
+    finally:
+        lib.pave_set_form_policy(prev)
+
+
+def form_plan(M, K, N, kind=FORM_ROWS, policy=None, planes=3):
+    """(order, ksplit) the dispatchers take for an [M, K] x [K, N] launch of `kind` (FORM_*) under `policy` (None:
+    the current one): pave_form_plan, a pure host function."""
+    lib = native.load()
+    order, parts = ctypes.c_int(), ctypes.c_int()
+    st = lib.pave_form_plan(int(M), int(K), int(N), int(kind), 16 if planes == PLANES_FP16 else int(planes),
+                            current_form_policy() if policy is None else int(policy), ctypes.byref(order),
+                            ctypes.byref(parts))
+    native.check(st, 'form_plan')
+    return order.value, parts.value
 
 
 class _Timed:
@@ -1180,8 +1220,10 @@ def gemm_bf16x3_ln(a, w_planes, bias, residual, gamma, beta, eps, out=None):
     else:
         _dev(out, 'out', torch.float32)
         _require(tuple(out.shape) == (M, N), 'gemm_bf16x3_ln: out [M,N]')
-    M1 = round_split_rows(M, 1)
-    if M1 is not None:      # (the last, nearly empty round of block slots as a launch of the small-row form)
+    # (the last, nearly empty round of block slots as a launch of the small-row form -- under a form policy
+    # (set_batch_invariant) the tail would take the head's LayerNorm form anyway: no split, one launch)
+    M1 = round_split_rows(M, 1) if current_form_policy() == 0 else None
+    if M1 is not None:
         gemm_bf16x3_ln(a[:M1], w_planes, bias, residual[:M1] if residual is not None else None, gamma, beta, eps,
                        out=out[:M1])
         gemm_bf16x3_ln(a[M1:], w_planes, bias, residual[M1:] if residual is not None else None, gamma, beta, eps,

@@ -24,6 +24,8 @@ indexing somebody else's cache.  ``encode(frames, into=slabs)`` appends to both.
 """
 import torch
 
+from .bricks import batch_invariant_scope
+
 
 class FrameSlabs(list):
     """The per-frame encoder memories of one video (a list of [S, C] tensors) together with what
@@ -80,6 +82,10 @@ class VideoPoseStream:
     def encode(self, frames, into=None):
         """frames [n, 3, H, W] on the device -> FrameSlabs of n memory slabs [S, C] (appended to
         `into`, a FrameSlabs of the same video, when given)."""
+        with batch_invariant_scope(self.model):
+            return self._encode(frames, into)
+
+    def _encode(self, frames, into):
         from .deform_attn import project_values_hoisted
         slabs = FrameSlabs() if into is None else into
         assert isinstance(slabs, FrameSlabs), 'encode(into=...) takes the FrameSlabs of an earlier encode()'
@@ -128,6 +134,10 @@ class VideoPoseStream:
         """Run head + decoders + OKS-NMS on windows of cached slabs (B = len(windows)).
         The two `force_*` index tensors pin the proposal / score top-k selections (parity tests:
         run-to-run rounding noise of the vendor GEMM / conv kernels can swap near-tied members)."""
+        with batch_invariant_scope(self.model):
+            return self._decode(slabs, windows, rescale, force_topk_proposals, force_score_topk)
+
+    def _decode(self, slabs, windows, rescale, force_topk_proposals, force_score_topk):
         T = self.T
         B = len(windows)
         dev = slabs[0].device
@@ -157,10 +167,11 @@ class VideoPoseStream:
     @torch.no_grad()
     def infer_video(self, frames, rescale=False):
         """frames [N, 3, H, W] -> list of N (bboxes, labels, kpts) tuples (device tensors)."""
-        slabs = self.encode(frames)
-        wins = self.window_indices(len(slabs), self.T)
-        results = []
-        for i in range(0, len(wins), self.decode_chunk):
-            res = self.decode(slabs, wins[i:i + self.decode_chunk], rescale=rescale)
-            results.extend(self.head.results_to_list(res))
-        return results
+        with batch_invariant_scope(self.model):
+            slabs = self.encode(frames)
+            wins = self.window_indices(len(slabs), self.T)
+            results = []
+            for i in range(0, len(wins), self.decode_chunk):
+                res = self.decode(slabs, wins[i:i + self.decode_chunk], rescale=rescale)
+                results.extend(self.head.results_to_list(res))
+            return results

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .bricks import (BaseModule, SourceKey, TransformerLayerSequence, batch_first, inverse_sigmoid,
-                     linear_norm, mlp_rows,
+                     linear_norm, mlp_rows, query_rows_scope,
                      seq_first_view, xavier_init)
 from .deform_attn import (MulFramesMultiScaleDeformableAttention,
                           MulFramesMultiScaleDeformablePoseAttention,
@@ -794,7 +794,8 @@ class VideoPoseTransformerMulFrames(Transformer):
             else:
                 tgt = torch.gather(output_memory, 1,
                                    topk_proposals.unsqueeze(-1).repeat(1, 1, self.embed_dims))
-            topk_kpts_unact = mlp_rows(kpt_branches[self.decoder.num_layers], tgt)
+            with query_rows_scope():   # (the proposals' rows: form policy 2 in a batch-invariant forward)
+                topk_kpts_unact = mlp_rows(kpt_branches[self.decoder.num_layers], tgt)
             fused_refs = None
             if fused and topk_kpts_unact.stride(-1) == 1:
                 fused_refs = ops.proposal_refs_(topk_kpts_unact, output_proposals, topk_proposals, T)
@@ -804,7 +805,8 @@ class VideoPoseTransformerMulFrames(Transformer):
                 topk_kpts_unact[..., 0::2] += top_props[..., 0:1]
                 topk_kpts_unact[..., 1::2] += top_props[..., 1:2]
             enc_outputs_kpt_unact = topk_kpts_unact
-            enc_outputs_sigma_unact = mlp_rows(sigma_branches[self.decoder.num_layers], tgt)
+            with query_rows_scope():
+                enc_outputs_sigma_unact = mlp_rows(sigma_branches[self.decoder.num_layers], tgt)
             if frame_shard is not None:
                 from . import dist as pdist
                 # (branch outputs off the 4-column grid are column slices of a padded matrix)
@@ -844,12 +846,13 @@ class VideoPoseTransformerMulFrames(Transformer):
                 [l.attentions[-1] for l in self.decoder.layers], memory, attn_mask,
                 masked_rows=mlvl_masks.masked_rows() if (attn_mask is not None
                                                          and hasattr(mlvl_masks, 'masked_rows')) else None)
-        inter_states, inter_references = self.decoder(
-            query=seq_first_view(query.contiguous()), key=None, value=seq_first_view(memory),
-            query_pos=seq_first_view(query_pos), key_padding_mask=attn_mask,
-            reference_points=reference_points, spatial_shapes=spatial_shapes,
-            level_start_index=level_start_index, valid_ratios=now_frame_valid_ratios,
-            **dec_kwargs)
+        with query_rows_scope():   # (the decoder's query rows; the hoisted value projections above keep the caller's)
+            inter_states, inter_references = self.decoder(
+                query=seq_first_view(query.contiguous()), key=None, value=seq_first_view(memory),
+                query_pos=seq_first_view(query_pos), key_padding_mask=attn_mask,
+                reference_points=reference_points, spatial_shapes=spatial_shapes,
+                level_start_index=level_start_index, valid_ratios=now_frame_valid_ratios,
+                **dec_kwargs)
         memory_out = seq_first_view(memory)
         if self.as_two_stage:
             return inter_states, init_reference_out, inter_references, enc_outputs_class, \
@@ -937,10 +940,11 @@ class VideoPoseTransformerMulFrames(Transformer):
                 [l.attentions[-1] for l in self.refine_decoder.layers], mem_bt, attn_mask,
                 masked_rows=mlvl_masks.masked_rows() if (attn_mask is not None
                                                          and hasattr(mlvl_masks, 'masked_rows')) else None)
-        inter_states, inter_references = self.refine_decoder(
-            query=seq_first_view(query.contiguous()), key=None, value=memory,
-            query_pos=seq_first_view(query_pos), key_padding_mask=attn_mask,
-            reference_points=reference_points, spatial_shapes=spatial_shapes,
-            level_start_index=level_start_index, valid_ratios=vr_rows,
-            memory_clip_index=img_inds, **dec_kwargs)
+        with query_rows_scope():
+            inter_states, inter_references = self.refine_decoder(
+                query=seq_first_view(query.contiguous()), key=None, value=memory,
+                query_pos=seq_first_view(query_pos), key_padding_mask=attn_mask,
+                reference_points=reference_points, spatial_shapes=spatial_shapes,
+                level_start_index=level_start_index, valid_ratios=vr_rows,
+                memory_clip_index=img_inds, **dec_kwargs)
         return inter_states, reference_points, inter_references
