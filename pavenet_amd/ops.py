@@ -200,6 +200,8 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
              grad_sampling_loc.shape == sampling_locations.shape and
              grad_attn_weight.shape == attention_weights.shape,
              'ms_deform_attn_backward: gradient shapes mismatch')
+    if grad_output.numel() == 0:   # no queries: nothing to add (the forward's empty result, as _ext does)
+        return
     fn = (lib.pave_ms_deform_attn_backward_f32 if dt == torch.float32
           else lib.pave_ms_deform_attn_backward_f64)
     with torch.cuda.device(value.device):

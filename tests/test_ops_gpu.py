@@ -605,10 +605,14 @@ def test_backward_vs_autograd_of_reference_formulation(D, dtype):
     aw = aw / aw.sum(-1, keepdim=True).sum(-2, keepdim=True)
     gout = torch.rand(N, Lq, M * D, generator=g).to(dtype)
     ref_in = [t.double().clone().requires_grad_(True) for t in (value, loc, aw)]
-    R.msda_forward_torch(ref_in[0], shapes, ref_in[1], ref_in[2]).backward(gout.double())
+    ref_out = R.msda_forward_torch(ref_in[0], shapes, ref_in[1], ref_in[2])
+    ref_out.backward(gout.double())
     dev_in = [t.cuda().clone().requires_grad_(True) for t in (value, loc, aw)]
     out = MultiScaleDeformableAttnFunction.apply(dev_in[0], shapes.cuda(), lsi.cuda(), dev_in[1],
                                                  dev_in[2], 2)
+    np.testing.assert_allclose(out.detach().double().cpu().numpy(), ref_out.detach().numpy(),
+                               **(dict(rtol=1e-12, atol=1e-15) if dtype == torch.float64 else
+                                  dict(rtol=1e-5, atol=1e-8)))
     out.backward(gout.cuda())
     tol = dict(rtol=1e-9, atol=1e-12) if dtype == torch.float64 else dict(rtol=2e-4, atol=1e-6)
     for a, b in zip(dev_in, ref_in):
