@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .ops import PLANES_FP16
 from .registry import (MMCV_ATTENTION, MMCV_FEEDFORWARD_NETWORK, MMCV_POSITIONAL_ENCODING,
                        MMCV_TRANSFORMER_LAYER, MMCV_TRANSFORMER_LAYER_SEQUENCE, build_attention,
                        build_feedforward_network, build_transformer_layer)
@@ -122,7 +123,7 @@ FUSE_QUERY_POS = False   # A/B switch (tools/ab_switch.py sets the attribute; ne
 _GEMM = {'mode': 'bf16x3', 'min_rows': 8192, 'ln_fused': True, 'small': True}
 
 
-_PLANES = {'bf16x3': 3, 'bf16x2': 2, 'bf16': 1, 'fp16': 16}   # 16 = ops.PLANES_FP16
+_PLANES = {'bf16x3': 3, 'bf16x2': 2, 'bf16': 1, 'fp16': PLANES_FP16}
 
 
 def set_gemm_mode(mode):

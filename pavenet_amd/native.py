@@ -7,80 +7,72 @@ or a symbol is absent, importing the product ops raises.
 import contextlib
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libpave_hip.so')
 DIAG_LIB_PATH = os.path.join(_HERE, 'lib', 'libpave_hip_diag.so')   # -DPAVE_DIAG build (tests/, tools/)
 
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'pave_hip.h')   # the only description of the ABI
+
 _c_int = ctypes.c_int
 _vp = ctypes.c_void_p
 
-# name -> argtypes; every entry point returns int (0 = PAVE_OK)
-SIGNATURES = {
-    'pave_ms_deform_attn_forward_f32': [_vp] * 6 + [_c_int] * 8 + [_vp],
-    'pave_ms_deform_attn_forward_f64': [_vp] * 6 + [_c_int] * 8 + [_vp],
-    'pave_deform_attn_grid_fused_f32': [_vp] * 10 + [_c_int] * 8 + [_vp, _c_int, _c_int, _vp],
-    'pave_deform_attn_pose_fused_f32': [_vp] * 8 + [_c_int] * 7 + [_vp, _c_int, _c_int, _vp],
-    'pave_fuse_sum_nhwc_f32': [_vp, _c_int] * 4 + [_vp] + [_c_int] * 5 + [_vp],
-    'pave_bias_act_rows_f32': [_vp] * 4 + [ctypes.c_longlong, _c_int, _c_int, _vp],
-    'pave_fill_rows_f32': [_vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _c_int, _vp],
-    'pave_bias_add_layernorm_f32': [_vp] * 6 + [ctypes.c_longlong, _c_int, ctypes.c_float, _vp],
-    'pave_bias_add_layernorm_pos_f32': [_vp] * 7 + [ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int,
-                                        ctypes.c_float, _vp],
-    'pave_enc_deform_attn_tile_f32': [_vp] * 4 + [_c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp],
-    'pave_ms_deform_attn_backward_f32': [_vp] * 9 + [_c_int] * 8 + [_vp],
-    'pave_ms_deform_attn_backward_f64': [_vp] * 9 + [_c_int] * 8 + [_vp],
-    'pave_preprocess_frames': [_vp, _c_int, _vp] + [_c_int] * 7 + [_vp, _vp, _c_int, _vp],
-    'pave_conv3x3_nhwc_f32': [_vp] * 4 + [_c_int] * 7 + [_vp],
-    'pave_rows_gemm_bias_res_act_f32': [_vp] * 7 + [ctypes.c_longlong] + [_c_int] * 4 + [_vp],
-    'pave_bias_relu_maxpool_nhwc_f32': [_vp] * 3 + [_c_int] * 4 + [_vp],
-    'pave_gemm_bf16x3_f32': [_vp] * 6 + [ctypes.c_longlong] + [_c_int] * 4 + [_vp],
-    'pave_gemm_fp16_act_f32': [_vp, _c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _c_int,
-                               ctypes.c_longlong, _c_int, _c_int, _c_int, _vp],
-    'pave_gemm_bf16x3_ex_f32': [_vp] * 5 + [ctypes.c_longlong, _vp, _vp, _c_int, ctypes.c_longlong]
-                               + [_c_int] * 4 + [_vp],
-    'pave_gemm_bf16x3_cat_f32': [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _c_int, _c_int,
-                                 _c_int, _c_int, _vp],
-    'pave_gemm_bf16x3_grouped_f32': [_vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _c_int, _c_int,
-                                     _c_int, _c_int, _c_int, _vp],
-    'pave_gemm_bf16x3_ln_f32': [_vp] * 6 + [ctypes.c_float, _vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp],
-    'pave_groupnorm_nhwc_f32': [_vp] * 4 + [ctypes.c_longlong] + [_c_int] * 4 + [ctypes.c_float, _vp,
-                                _c_int, _vp, _vp],
-    'pave_groupnorm_levels_nhwc_f32': [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
-    'pave_ref_update_f32': [_vp, _vp, _vp, ctypes.c_longlong, ctypes.c_float, _vp],
-    'pave_conv7x7s2_nchw_split_f32': [_vp] * 4 + [_c_int] * 7 + [_vp],
-    'pave_repitch_rows_f32': [_vp, _vp, ctypes.c_longlong, _c_int, _c_int, _vp],
-    'pave_conv1x1_strided_split_f32': [_vp] * 4 + [_c_int] * 8 + [_vp],
-    'pave_split_bf16x3_f32': [_vp, _vp, ctypes.c_longlong, _c_int, _vp],
-    'pave_conv3x3_split_f32': [_vp] * 5 + [_c_int] * 8 + [_vp],
-    'pave_bottleneck_chain_f32': [_vp] * 8 + [_c_int, _vp, _vp, _vp, _vp] + [_c_int] * 5 + [_vp],
-    'pave_conv3x3_splitk_f32': [_vp] * 5 + [_c_int] * 7 + [_vp, ctypes.c_longlong, _c_int, _vp],
-    'pave_gemm_bf16x3_encproj_f32': [_vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp,
-                                     ctypes.c_longlong, _c_int, _c_int, _vp],
-    'pave_conv3x3s2_c3_nchw_f32': [_vp] * 4 + [_c_int] * 4 + [_vp],
-    'pave_mha_core_f32': [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp],
-    'pave_topk_rows_f32': [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp],
-    'pave_gather_frame_poses_f32': [_vp, _vp, _vp] + [_c_int] * 5 + [_vp],
-    'pave_pose_finalize_f32': [_vp] * 7 + [_c_int] * 5 + [_vp],
-    'pave_ref_update_frames_f32': [_vp, _vp, _vp] + [_c_int] * 5 + [ctypes.c_float, _vp],
-    'pave_swin_window_attn_f32': [_vp] * 4 + [_c_int] * 7 + [ctypes.c_float, _vp],
-    'pave_merge_softmax_partials_f32': [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp],
-    'pave_gemm_bf16x3_splitk_f32': [_vp] * 5 + [ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _vp,
-                                    ctypes.c_longlong, _vp],
-    'pave_gather_rows_add_f32': [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp] + [_c_int] * 4 + [_vp],
-    'pave_proposal_refs_f32': [_vp, _c_int, _vp, ctypes.c_longlong, _vp, _vp] + [_c_int] * 5 + [_vp],
-    'pave_oks_nms_f32': [_vp] * 3 + [ctypes.c_double] + [_vp] * 2 + [_c_int] * 3 + [_vp],
-    'pave_preprocess_frames_flip': [_vp, _c_int, _vp] + [_c_int] * 7 + [_vp, _vp, _c_int, _vp],
-    'pave_aug_merge_nms_f32': [_vp, ctypes.c_float, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                               _c_int] + [_vp] * 7,
-    'pave_hflip_canvas_f32': [_vp, _vp, _vp] + [_c_int] * 5 + [_vp],
-    'pave_set_form_policy': [_c_int],
-    'pave_form_plan': [ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
-}
-# every symbol include/pave_hip.h declares
-EXPORTED = tuple(SIGNATURES) + ('pave_abi_version', 'pave_last_error', 'pave_conv3x3_splitk_workspace_bytes',
-                                'pave_gemm_splitk_workspace_bytes', 'pave_get_form_policy')
 
+class NativeLibraryError(RuntimeError):
+    pass
+
+
+_SCALARS = {'int': _c_int, 'long long': ctypes.c_longlong, 'float': ctypes.c_float, 'double': ctypes.c_double}
+_RESTYPES = {'int': _c_int, 'long long': ctypes.c_longlong, 'const char*': ctypes.c_char_p}
+
+
+def parse_header(text):
+    """(functions, defines) of a C header in the style of include/pave_hip.h: functions[name] = (restype, argtypes)
+    for every `ret pave_name(args);`, defines[name] = int for every integer `#define PAVE_*`.  A parameter is a
+    pointer (c_void_p) or an int / long long / float / double by value.  Nothing is guessed: ctypes calls a function
+    it has no argtypes for with C ints and truncates pointers without a word, so a `pave_name(` that is not part of
+    a declaration typed here, or a parameter of any other type, raises NativeLibraryError."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    defines = {m.group(1): int(m.group(2)) for m in
+               re.finditer(r'^[ \t]*#[ \t]*define[ \t]+(PAVE_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
+    functions = {}
+    for m in re.finditer(r'([\w\s*]+?)\b(pave_\w+)\s*\(([^()]*)\)\s*;', text):
+        ret, name, params = re.sub(r'\s*\*\s*', '*', ' '.join(m.group(1).split())), m.group(2), m.group(3).strip()
+        if ret not in _RESTYPES:
+            raise NativeLibraryError(f'{name}: return type {ret!r} is not one of {sorted(_RESTYPES)}')
+        argtypes = []
+        for p in ([] if params == 'void' else params.split(',')):
+            if '*' in p:
+                argtypes.append(_vp)
+                continue
+            kind = ' '.join(w for w in p.split()[:-1] if w != 'const')     # (the last word is the parameter's name)
+            if kind not in _SCALARS or '[' in p:
+                raise NativeLibraryError(f'{name}: parameter {" ".join(p.split())!r} is neither a pointer nor one of '
+                                         f'{sorted(_SCALARS)}')
+            argtypes.append(_SCALARS[kind])
+        functions[name] = (_RESTYPES[ret], argtypes)
+    untyped = sorted(set(re.findall(r'\b(pave_\w+)\s*\(', text)) - set(functions))
+    if untyped:
+        raise NativeLibraryError(f'{", ".join(untyped)}: not a declaration of the form `ret pave_name(args);`')
+    return functions, defines
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise NativeLibraryError(f'{HEADER_PATH} not readable ({e}): pavenet_amd types its entry points from the '
+                                 f'header, there is no second table') from None
+
+
+FUNCTIONS, DEFINES = _read_header()
+EXPORTED = tuple(FUNCTIONS)        # every symbol include/pave_hip.h declares
+# name -> argtypes of the entry points that return a status (0 = PAVE_OK): int, with arguments
+SIGNATURES = {name: argtypes for name, (restype, argtypes) in FUNCTIONS.items() if restype is _c_int and argtypes}
+ABI_VERSION = DEFINES['PAVE_ABI_VERSION']
 
 
 class GnLevel(ctypes.Structure):
@@ -90,7 +82,7 @@ class GnLevel(ctypes.Structure):
                 ('eps', ctypes.c_float)]
 
 
-AUG_MAX_AUGS, AUG_MAX_SLOTS, AUG_MAX_K = 16, 128, 64
+AUG_MAX_AUGS, AUG_MAX_SLOTS, AUG_MAX_K = (DEFINES['PAVE_AUG_MAX_' + n] for n in ('AUGS', 'SLOTS', 'K'))
 
 
 class AugPlan(ctypes.Structure):
@@ -103,11 +95,6 @@ class AugPlan(ctypes.Structure):
 
 
 _lib = None
-ABI_VERSION = 21  # == PAVE_ABI_VERSION of include/pave_hip.h this file's SIGNATURES were written for
-
-
-class NativeLibraryError(RuntimeError):
-    pass
 
 
 def _open(path):
@@ -123,22 +110,12 @@ def _open(path):
         raise NativeLibraryError(
             f'{path} lacks {", ".join(missing)} (built from older sources): rebuild it '
             f'(`python -m pavenet_amd.build_native`)')
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in FUNCTIONS.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        fn.restype = _c_int
-    lib.pave_abi_version.restype = _c_int
-    lib.pave_abi_version.argtypes = []
-    lib.pave_last_error.restype = ctypes.c_char_p
-    lib.pave_last_error.argtypes = []
-    lib.pave_conv3x3_splitk_workspace_bytes.restype = ctypes.c_longlong
-    lib.pave_conv3x3_splitk_workspace_bytes.argtypes = [_c_int] * 6
-    lib.pave_gemm_splitk_workspace_bytes.restype = ctypes.c_longlong
-    lib.pave_gemm_splitk_workspace_bytes.argtypes = [ctypes.c_longlong, _c_int, _c_int]
-    lib.pave_get_form_policy.restype = _c_int
-    lib.pave_get_form_policy.argtypes = []
+        fn.restype = restype
     have = lib.pave_abi_version()
-    if have != ABI_VERSION:   # a stale .so called with the wrong argument list corrupts memory
+    if have != ABI_VERSION:   # a stale .so against a newer header: the wrong argument list corrupts memory
         raise NativeLibraryError(
             f'{path} has ABI version {have}, this package expects {ABI_VERSION}: rebuild it '
             f'(`python -m pavenet_amd.build_native`)')

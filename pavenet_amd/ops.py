@@ -38,8 +38,12 @@ def _stream_ptr():
 # Form policy of the GEMM / convolution dispatchers (pave_set_form_policy, include/pave_hip.h): 0 = the selection
 # by row count, 1 = tile order, 2 = K-split order where it applies.  Under 1 and 2 an output row is a function of
 # its own input row only, whatever the batch (bricks.set_batch_invariant).
-FORM_ROWS, FORM_ROWS_SPLITK, FORM_ROWS_TILE, FORM_LN, FORM_CONV3X3, FORM_CONV1X1S, FORM_ENCPROJ = range(7)
-ORDER_TILE, ORDER_KSPLIT, ORDER_SPLITK, ORDER_TILE_LNPASS, ORDER_KSPLIT_LNPASS, ORDER_TILE_LN8 = range(6)
+FORM_ROWS, FORM_ROWS_SPLITK, FORM_ROWS_TILE, FORM_LN, FORM_CONV3X3, FORM_CONV1X1S, FORM_ENCPROJ = (
+    native.DEFINES['PAVE_FORM_' + n] for n in ('ROWS', 'ROWS_SPLITK', 'ROWS_TILE', 'LN', 'CONV3X3', 'CONV1X1S',
+                                               'ENCPROJ'))
+ORDER_TILE, ORDER_KSPLIT, ORDER_SPLITK, ORDER_TILE_LNPASS, ORDER_KSPLIT_LNPASS, ORDER_TILE_LN8 = (
+    native.DEFINES['PAVE_ORDER_' + n] for n in ('TILE', 'KSPLIT', 'SPLITK', 'TILE_LNPASS', 'KSPLIT_LNPASS',
+                                                'TILE_LN8'))
 
 
 def current_form_policy():
@@ -115,7 +119,26 @@ def _dev(t, name, dtype=None):
     return t
 
 
-PLANES_FP16 = 16   # include/pave_hip.h PAVE_PLANES_FP16: one plane of fp16 operands
+def _nhwc(x, who):
+    _require(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4, f'{who}: fp32 4-D')
+    _require(x.is_contiguous(memory_format=torch.channels_last), f'{who}: channels_last input')
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _launch(entry, what, dev, *args, tag=None, flops=0, shape=None):
+    """What every launch must meet, in one place: the entry point of include/pave_hip.h looked up on the library of
+    the moment (native.diag_build() swaps it), called on `dev` with the current stream as its last argument, timed
+    when `tag` is one bench.py asked for, and its status checked under the name `what`."""
+    fn = getattr(native.load(), entry)
+    with torch.cuda.device(dev), _Timed(tag, flops, shape):
+        st = fn(*args, _stream_ptr())
+    native.check(st, what)
+
+
+PLANES_FP16 = native.DEFINES['PAVE_PLANES_FP16']   # one plane of fp16 operands
 
 
 def _planes(w_planes, name='w_planes', fp16=False, only=None):
@@ -145,7 +168,6 @@ def ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
                            sampling_locations, attention_weights, im2col_step=64):
     """[R1] value [bs,S,M,D], shapes [L,2] i64, lsi [L] i64, loc [bs,Lq,M,L,P,2],
     weights [bs,Lq,M,L,P] -> [bs, Lq, M*D]."""
-    lib = native.load()
     _require(value.dtype in (torch.float32, torch.float64),
              'ms_deform_attn_forward: value must be float32 or float64')
     dt = value.dtype
@@ -168,14 +190,12 @@ def ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
     out = torch.empty((bs, Lq, M * D), dtype=dt, device=value.device)
     if out.numel() == 0:   # no queries (or empty batch): empty result, as the PyTorch formulation
         return out         # (MO:92-149) gives; the C entry point rejects non-positive sizes
-    fn = (lib.pave_ms_deform_attn_forward_f32 if dt == torch.float32
-          else lib.pave_ms_deform_attn_forward_f64)
-    with torch.cuda.device(value.device):
-        st = fn(value.data_ptr(), value_spatial_shapes.data_ptr(),
-                value_level_start_index.data_ptr(), sampling_locations.data_ptr(),
-                attention_weights.data_ptr(), out.data_ptr(), bs, S, M, D, L, Lq, P,
-                int(im2col_step), _stream_ptr())
-    native.check(st, 'ms_deform_attn_forward')
+    _launch('pave_ms_deform_attn_forward_f32' if dt == torch.float32 else 'pave_ms_deform_attn_forward_f64',
+            'ms_deform_attn_forward', value.device,
+            value.data_ptr(), value_spatial_shapes.data_ptr(),
+            value_level_start_index.data_ptr(), sampling_locations.data_ptr(),
+            attention_weights.data_ptr(), out.data_ptr(), bs, S, M, D, L, Lq, P,
+            int(im2col_step))
     return out
 
 
@@ -184,7 +204,6 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
                             grad_sampling_loc, grad_attn_weight, im2col_step=64):
     """Same positional / keyword surface as ``mmcv._ext.ms_deform_attn_backward``
     (pybind.cpp:743-748): grad_value is accumulated into, the other two are overwritten."""
-    lib = native.load()
     dt = value.dtype
     _require(dt in (torch.float32, torch.float64), 'ms_deform_attn_backward: fp32 / fp64 only')
     for t, n in ((value, 'value'), (sampling_locations, 'sampling_loc'),
@@ -202,15 +221,13 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
              'ms_deform_attn_backward: gradient shapes mismatch')
     if grad_output.numel() == 0:   # no queries: nothing to add (the forward's empty result, as _ext does)
         return
-    fn = (lib.pave_ms_deform_attn_backward_f32 if dt == torch.float32
-          else lib.pave_ms_deform_attn_backward_f64)
-    with torch.cuda.device(value.device):
-        st = fn(value.data_ptr(), value_spatial_shapes.data_ptr(),
-                value_level_start_index.data_ptr(), sampling_locations.data_ptr(),
-                attention_weights.data_ptr(), grad_output.data_ptr(), grad_value.data_ptr(),
-                grad_sampling_loc.data_ptr(), grad_attn_weight.data_ptr(), bs, S, M, D, L, Lq, P,
-                int(im2col_step), _stream_ptr())
-    native.check(st, 'ms_deform_attn_backward')
+    _launch('pave_ms_deform_attn_backward_f32' if dt == torch.float32 else 'pave_ms_deform_attn_backward_f64',
+            'ms_deform_attn_backward', value.device,
+            value.data_ptr(), value_spatial_shapes.data_ptr(),
+            value_level_start_index.data_ptr(), sampling_locations.data_ptr(),
+            attention_weights.data_ptr(), grad_output.data_ptr(), grad_value.data_ptr(),
+            grad_sampling_loc.data_ptr(), grad_attn_weight.data_ptr(), bs, S, M, D, L, Lq, P,
+            int(im2col_step))
 
 
 class MultiScaleDeformableAttnFunction(torch.autograd.Function):
@@ -267,7 +284,6 @@ def deform_attn_grid_fused(value, spatial_shapes, level_start_index, proj, ref, 
         _require(frame_table is None, 'deform_attn_grid_fused: frame_table is an inference-only option')
         return GridFusedFunction.apply(value, spatial_shapes, level_start_index, proj, ref, T,
                                        n_clips, units_per_clip, unit_clip, order)
-    lib = native.load()
     f32 = torch.float32
     _dev(value, 'value', f32)
     _dev(spatial_shapes, 'spatial_shapes', torch.int64)
@@ -302,18 +318,12 @@ def deform_attn_grid_fused(value, spatial_shapes, level_start_index, proj, ref, 
         smax = torch.empty((n_units, 8), dtype=f32, device=value.device)
         ssum = torch.empty((n_units, 8), dtype=f32, device=value.device)
     tag = 'enc_grid_T1' if (T == 1 and unit_clip is None) else f'grid_T{T}'
-    with torch.cuda.device(value.device), _Timed(tag):
-        st = lib.pave_deform_attn_grid_fused_f32(
+    _launch('pave_deform_attn_grid_fused_f32', 'deform_attn_grid_fused', value.device,
             value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-            proj.data_ptr(), ref.data_ptr(),
-            unit_clip.data_ptr() if unit_clip is not None else None,
-            order.data_ptr() if order is not None else None, out.data_ptr(),
-            smax.data_ptr() if return_stats else None,
-            ssum.data_ptr() if return_stats else None, n_units, int(units_per_clip),
+            proj.data_ptr(), ref.data_ptr(), _ptr(unit_clip), _ptr(order), out.data_ptr(),
+            _ptr(smax), _ptr(ssum), n_units, int(units_per_clip),
             int(n_clips), int(T), S, L, 4, proj.stride(0),
-            frame_table.data_ptr() if frame_table is not None else None, int(value.shape[0]), ref_levels,
-            _stream_ptr())
-    native.check(st, 'deform_attn_grid_fused')
+            _ptr(frame_table), int(value.shape[0]), ref_levels, tag=tag)
     if return_stats:
         return out, smax, ssum
     return out
@@ -333,7 +343,6 @@ def deform_attn_pose_fused(value, spatial_shapes, level_start_index, proj, ref, 
         _require(frame_table is None, 'deform_attn_pose_fused: frame_table is an inference-only option')
         return PoseFusedFunction.apply(value, spatial_shapes, level_start_index, proj, ref, T,
                                        n_clips, int(num_query), int(num_keypoints))
-    lib = native.load()
     f32 = torch.float32
     _dev(value, 'value', f32)
     _dev(spatial_shapes, 'spatial_shapes', torch.int64)
@@ -360,15 +369,11 @@ def deform_attn_pose_fused(value, spatial_shapes, level_start_index, proj, ref, 
     if return_stats:
         smax = torch.empty((n_clips * Q, 8), dtype=f32, device=value.device)
         ssum = torch.empty((n_clips * Q, 8), dtype=f32, device=value.device)
-    with torch.cuda.device(value.device), _Timed(f'pose_T{T}'):
-        st = lib.pave_deform_attn_pose_fused_f32(
+    _launch('pave_deform_attn_pose_fused_f32', 'deform_attn_pose_fused', value.device,
             value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-            proj.data_ptr(), ref.data_ptr(), out.data_ptr(),
-            smax.data_ptr() if return_stats else None,
-            ssum.data_ptr() if return_stats else None, int(n_clips), Q, int(T), S, L, K,
-            proj.stride(0), frame_table.data_ptr() if frame_table is not None else None,
-            int(value.shape[0]), ref_levels, _stream_ptr())
-    native.check(st, 'deform_attn_pose_fused')
+            proj.data_ptr(), ref.data_ptr(), out.data_ptr(), _ptr(smax), _ptr(ssum),
+            int(n_clips), Q, int(T), S, L, K, proj.stride(0), _ptr(frame_table),
+            int(value.shape[0]), ref_levels, tag=f'pose_T{T}')
     if return_stats:
         return out, smax, ssum
     return out
@@ -377,7 +382,6 @@ def deform_attn_pose_fused(value, spatial_shapes, level_start_index, proj, ref, 
 def oks_nms(kpts, scores, sigmas, thresh):
     """Device OKS-NMS (HEAD:1624-1665).  kpts [n_clips, N, K, 3], scores [n_clips, N],
     sigmas [K] float64 -> (keep [n_clips, N] int32, order [n_clips, N] int32)."""
-    lib = native.load()
     _dev(kpts, 'kpts', torch.float32)
     _dev(scores, 'scores', torch.float32)
     _dev(sigmas, 'sigmas', torch.float64)
@@ -389,11 +393,8 @@ def oks_nms(kpts, scores, sigmas, thresh):
     order = torch.empty((n_clips, N), dtype=torch.int32, device=kpts.device)
     if keep.numel() == 0:  # nothing to suppress (the NumPy loop of HEAD:1624-1665 returns [])
         return keep, order
-    with torch.cuda.device(kpts.device):
-        st = lib.pave_oks_nms_f32(kpts.data_ptr(), scores.data_ptr(), sigmas.data_ptr(),
-                                  float(thresh), keep.data_ptr(), order.data_ptr(), n_clips, N,
-                                  K, _stream_ptr())
-    native.check(st, 'oks_nms')
+    _launch('pave_oks_nms_f32', 'oks_nms', kpts.device, kpts.data_ptr(), scores.data_ptr(), sigmas.data_ptr(),
+            float(thresh), keep.data_ptr(), order.data_ptr(), n_clips, N, K)
     return keep, order
 
 
@@ -409,7 +410,6 @@ def aug_merge_nms(bboxes, kpts, keeps, flips, img_w, scale_factor, flip_perm, *,
     method: 'nms' (hard) or the soft-NMS kinds 'naive' / 'linear' / 'gaussian'.
     -> dict(dets [B, M, 5], labels [B, M] int64, kpts [B, M, K, 3], inds [B, M] int64, keep [B, M] int32,
     count [B] int32), M = min(max_num, A N) (A N when max_num <= 0); rows past count[b] have keep 0 and inds -1."""
-    lib = native.load()
     A = len(bboxes)
     _require(0 < A <= native.AUG_MAX_AUGS, f'aug_merge_nms: 1 .. {native.AUG_MAX_AUGS} augmentations, got {A}')
     _require(len(kpts) == A and len(keeps) == A and len(flips) == A and len(img_w) == A and
@@ -442,7 +442,7 @@ def aug_merge_nms(bboxes, kpts, keeps, flips, img_w, scale_factor, flip_perm, *,
     for a in range(A):
         plan.bboxes[a] = bboxes[a].data_ptr()
         plan.kpts[a] = kpts[a].data_ptr()
-        plan.keep[a] = keeps[a].data_ptr() if keeps[a] is not None else None
+        plan.keep[a] = _ptr(keeps[a])
         plan.flip[a] = int(bool(flips[a]))
         for b in range(B):
             plan.img_w[a * B + b] = float(img_w[a][b])
@@ -461,12 +461,10 @@ def aug_merge_nms(bboxes, kpts, keeps, flips, img_w, scale_factor, flip_perm, *,
     inds = torch.empty((B, M), dtype=torch.int64, device=dev)
     keep = torch.empty((B, M), dtype=torch.int32, device=dev)
     count = torch.empty((B,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = lib.pave_aug_merge_nms_f32(ctypes.byref(plan), float(score_thr), int(max_num), NMS_METHODS[method],
-                                        float(iou_thr), float(sigma), float(min_score), int(offset),
-                                        dets.data_ptr(), labels.data_ptr(), out_k.data_ptr(), inds.data_ptr(),
-                                        keep.data_ptr(), count.data_ptr(), _stream_ptr())
-    native.check(st, 'aug_merge_nms')
+    _launch('pave_aug_merge_nms_f32', 'aug_merge_nms', dev, ctypes.byref(plan), float(score_thr), int(max_num),
+            NMS_METHODS[method], float(iou_thr), float(sigma), float(min_score), int(offset),
+            dets.data_ptr(), labels.data_ptr(), out_k.data_ptr(), inds.data_ptr(),
+            keep.data_ptr(), count.data_ptr())
     return dict(dets=dets, labels=labels, kpts=out_k, inds=inds, keep=keep, count=count)
 
 
@@ -474,7 +472,6 @@ def hflip_canvas(x, valid_w):
     """Horizontal flip of preprocessed canvases x [n, C, Hp, Wp] fp32 (pave_hflip_canvas_f32), out of place:
     columns [0, w) of image i mirrored within themselves, w = valid_w (an int for all images, or a device int32
     tensor [n]); the padding columns from w on are copied unchanged."""
-    lib = native.load()
     _dev(x, 'x', torch.float32)
     _require(x.dim() == 4, 'hflip_canvas: x must be [n, C, Hp, Wp]')
     n, C, Hp, Wp = x.shape
@@ -488,9 +485,7 @@ def hflip_canvas(x, valid_w):
     y = torch.empty_like(x)
     if x.numel() == 0:
         return y
-    with torch.cuda.device(x.device):
-        st = lib.pave_hflip_canvas_f32(x.data_ptr(), y.data_ptr(), w_ptr, w_all, n, C, Hp, Wp, _stream_ptr())
-    native.check(st, 'hflip_canvas')
+    _launch('pave_hflip_canvas_f32', 'hflip_canvas', x.device, x.data_ptr(), y.data_ptr(), w_ptr, w_all, n, C, Hp, Wp)
     return y
 
 
@@ -499,7 +494,6 @@ def fuse_sum_nhwc(terms, relu=True):
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones
     read through a nearest-neighbour up-sampling by 2^shift) [N, C, H, W] channels_last, summed in
     the order given (hrnet.py:197-214)."""
-    lib = native.load()
     _require(1 <= len(terms) <= 4, 'fuse_sum_nhwc: 1..4 terms')
     t0, s0 = terms[0]
     N, C = t0.shape[0], t0.shape[1]
@@ -514,16 +508,14 @@ def fuse_sum_nhwc(terms, relu=True):
         args += [t.data_ptr(), int(sh)]
     args += [None, 0] * (4 - len(terms))
     y = torch.empty((N, H, W, C), dtype=torch.float32, device=t0.device)
-    with torch.cuda.device(t0.device), _Timed('fuse_sum'):
-        st = lib.pave_fuse_sum_nhwc_f32(*args, y.data_ptr(), N, H, W, C, int(bool(relu)), _stream_ptr())
-    native.check(st, 'fuse_sum_nhwc')
+    _launch('pave_fuse_sum_nhwc_f32', 'fuse_sum_nhwc', t0.device, *args, y.data_ptr(), N, H, W, C, int(bool(relu)),
+            tag='fuse_sum')
     return y.permute(0, 3, 1, 2)
 
 
 def bias_act_rows_(x, bias=None, res=None, relu=True):
     """In place: x[r, c] = act(x[r, c] + bias[c] + res[r, c]) over the last (channel) dim.
     `x` must be dense with channels innermost (token matrix, or an NHWC / channels_last map)."""
-    lib = native.load()
     _require(x.is_cuda and x.dtype == torch.float32, 'bias_act_rows_: fp32 device tensor')
     nhwc = x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) \
         and not x.is_contiguous()
@@ -538,30 +530,22 @@ def bias_act_rows_(x, bias=None, res=None, relu=True):
         if res is not None:
             _require(res.shape == x.shape and res.is_contiguous(), 'bias_act_rows_: residual layout')
     rows = x.numel() // C
-    with torch.cuda.device(x.device), _Timed('bias_act_rows'):
-        st = lib.pave_bias_act_rows_f32(
-            x.data_ptr(), bias.data_ptr() if bias is not None else None,
-            res.data_ptr() if res is not None else None, x.data_ptr(), rows, C, int(bool(relu)),
-            _stream_ptr())
-    native.check(st, 'bias_act_rows')
+    _launch('pave_bias_act_rows_f32', 'bias_act_rows', x.device,
+            x.data_ptr(), _ptr(bias), _ptr(res), x.data_ptr(), rows, C, int(bool(relu)), tag='bias_act_rows')
     return x
 
 
 def fill_rows_(x, rows, values=None):
     """x[rows] = values (zeros when None), in place: x [R, C] fp32 (a row-strided view is fine), rows int32
     indices on the device, values [C] -- pave_fill_rows_f32."""
-    lib = native.load()
     _require(x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1,
              'fill_rows_: x [R, C] fp32 on the device, unit column stride')
     _dev(rows, 'rows', torch.int32)
     if values is not None:
         _dev(values, 'values', torch.float32)
         _require(values.numel() == x.shape[1], 'fill_rows_: values [C]')
-    with torch.cuda.device(x.device):
-        st = lib.pave_fill_rows_f32(x.data_ptr(), x.stride(0), x.shape[0], rows.data_ptr(), rows.numel(),
-                                    values.data_ptr() if values is not None else None, x.shape[1],
-                                    _stream_ptr())
-    native.check(st, 'fill_rows_')
+    _launch('pave_fill_rows_f32', 'fill_rows_', x.device, x.data_ptr(), x.stride(0), x.shape[0], rows.data_ptr(),
+            rows.numel(), _ptr(values), x.shape[1])
     return x
 
 
@@ -569,7 +553,6 @@ def bias_add_layernorm(x, bias, res, gamma, beta, eps=1e-5, pos=None):
     """LayerNorm(x + bias + res) over the last dim; x / res dense row-major [..., C].
     With pos ([P, C] rows, P dividing the row count pattern r % P): returns (y, y + pos) from the
     same pass (the next layer's `query + query_pos`)."""
-    lib = native.load()
     _dev(x, 'x', torch.float32)
     C = x.shape[-1]
     if res is not None:
@@ -577,24 +560,18 @@ def bias_add_layernorm(x, bias, res, gamma, beta, eps=1e-5, pos=None):
                  'bias_add_layernorm: residual must match x')
     out = torch.empty_like(x)
     rows = x.numel() // C
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     if pos is None:
-        with torch.cuda.device(x.device), _Timed('bias_add_layernorm'):
-            st = lib.pave_bias_add_layernorm_f32(x.data_ptr(), ptr(bias), ptr(res), gamma.data_ptr(),
-                                                 beta.data_ptr(), out.data_ptr(), rows, C,
-                                                 float(eps), _stream_ptr())
-        native.check(st, 'bias_add_layernorm')
+        _launch('pave_bias_add_layernorm_f32', 'bias_add_layernorm', x.device,
+                x.data_ptr(), _ptr(bias), _ptr(res), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), rows, C,
+                float(eps), tag='bias_add_layernorm')
         return out
     _dev(pos, 'pos', torch.float32)
     _require(pos.shape[-1] == C and rows % (pos.numel() // C) == 0,
              'bias_add_layernorm: pos [P, C] with P dividing the number of rows')
     out_plus = torch.empty_like(x)
-    with torch.cuda.device(x.device), _Timed('bias_add_layernorm'):
-        st = lib.pave_bias_add_layernorm_pos_f32(
-            x.data_ptr(), ptr(bias), ptr(res), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
-            pos.data_ptr(), pos.numel() // C, out_plus.data_ptr(), rows, C, float(eps),
-            _stream_ptr())
-    native.check(st, 'bias_add_layernorm')
+    _launch('pave_bias_add_layernorm_pos_f32', 'bias_add_layernorm', x.device,
+            x.data_ptr(), _ptr(bias), _ptr(res), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
+            pos.data_ptr(), pos.numel() // C, out_plus.data_ptr(), rows, C, float(eps), tag='bias_add_layernorm')
     return out, out_plus
 
 
@@ -623,7 +600,6 @@ def gemm_bf16x3_encproj(a, w_planes, table, ref, levels_hw, value_bias=None, out
     -> (value [M, 256], samp [M, 384]): samp = level pixel coordinates + attention weights, the
     `prepared=True` input of deform_attn_enc_tile.  value_bias [256]: added to the value columns
     instead of table[:, :256] (not read then: value_proj has no positional term)."""
-    lib = native.load()
     for t, nm in ((a, 'a'), (table, 'table'), (ref, 'ref')):
         _dev(t, nm, torch.float32)
     npl = _planes(w_planes, only=_Q_PLANES)
@@ -636,7 +612,6 @@ def gemm_bf16x3_encproj(a, w_planes, table, ref, levels_hw, value_bias=None, out
     if value_bias is not None:
         _dev(value_bias, 'value_bias', torch.float32)
         _require(value_bias.numel() == 256 and value_bias.is_contiguous(), 'gemm_bf16x3_encproj: value_bias [256]')
-    import ctypes
     hw_arr = (ctypes.c_int * 8)(*[int(v) for hw in levels_hw for v in hw])
     if out is not None:     # (value [M, 256], samp [M, 384]) given: row slices of larger dense matrices
         value, samp = out
@@ -646,14 +621,10 @@ def gemm_bf16x3_encproj(a, w_planes, table, ref, levels_hw, value_bias=None, out
     else:
         value = torch.empty((M, 256), dtype=torch.float32, device=a.device)
         samp = torch.empty((M, 384), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device), _Timed('gemm_bf16x3', 2 * M * K * 640, (M, K, 640, 'encproj')):
-        st = lib.pave_gemm_bf16x3_encproj_f32(a.data_ptr(), w_planes.data_ptr(), table.data_ptr(),
-                                              table.shape[0],
-                                              value_bias.data_ptr() if value_bias is not None else None,
-                                              ref.data_ptr(),
-                                              ctypes.cast(hw_arr, ctypes.c_void_p), value.data_ptr(),
-                                              samp.data_ptr(), M, K, npl, _stream_ptr())
-    native.check(st, 'gemm_bf16x3_encproj')
+    _launch('pave_gemm_bf16x3_encproj_f32', 'gemm_bf16x3_encproj', a.device,
+            a.data_ptr(), w_planes.data_ptr(), table.data_ptr(), table.shape[0], _ptr(value_bias), ref.data_ptr(),
+            ctypes.cast(hw_arr, ctypes.c_void_p), value.data_ptr(), samp.data_ptr(), M, K, npl,
+            tag='gemm_bf16x3', flops=2 * M * K * 640, shape=(M, K, 640, 'encproj'))
     return value, samp
 
 
@@ -670,7 +641,6 @@ def deform_attn_enc_tile(value, proj, ref, *, levels_hw, variant=0, window_shift
             (value.requires_grad or proj.requires_grad or ref.requires_grad):
         from .fused_autograd import EncTileFunction
         return EncTileFunction.apply(value, proj, ref, levels_hw, variant)
-    lib = native.load()
     f32 = torch.float32
     _dev(value, 'value', f32)
     _dev(proj, 'proj', f32)
@@ -687,7 +657,6 @@ def deform_attn_enc_tile(value, proj, ref, *, levels_hw, variant=0, window_shift
     _require(proj.dim() == 2 and proj.shape[0] == F_ * S, 'deform_attn_enc_tile: proj rows')
     _require(ref is None or ref.numel() == F_ * S * 8, 'deform_attn_enc_tile: ref must be [F*S, 4, 2]')
     _require(enc_tile_supported(levels_hw), 'deform_attn_enc_tile: needs a 4-level halving pyramid')
-    import ctypes
     flat = [int(v) for hw in levels_hw for v in hw]
     hw_arr = (ctypes.c_int * 8)(*flat)
     sh_arr = None
@@ -695,12 +664,10 @@ def deform_attn_enc_tile(value, proj, ref, *, levels_hw, variant=0, window_shift
         _require(len(window_shift) == 64, 'deform_attn_enc_tile: window_shift has 64 entries')
         sh_arr = (ctypes.c_int * 64)(*[int(v) for v in window_shift])
     out = torch.empty((F_ * S, 256), dtype=torch.float16 if out_half else f32, device=value.device)
-    with torch.cuda.device(value.device), _Timed('enc_tile'):
-        st = lib.pave_enc_deform_attn_tile_f32(
-            value.data_ptr(), proj.data_ptr(), ref.data_ptr() if ref is not None else None,
+    _launch('pave_enc_deform_attn_tile_f32', 'deform_attn_enc_tile', value.device,
+            value.data_ptr(), proj.data_ptr(), _ptr(ref),
             out.data_ptr(), F_, S, ctypes.cast(hw_arr, ctypes.c_void_p), proj.stride(0), int(variant),
-            ctypes.cast(sh_arr, ctypes.c_void_p) if sh_arr is not None else None, _stream_ptr())
-    native.check(st, 'deform_attn_enc_tile')
+            ctypes.cast(sh_arr, ctypes.c_void_p) if sh_arr is not None else None, tag='enc_tile')
     return out
 
 
@@ -708,21 +675,15 @@ def conv3x3_nhwc(x, w_taps, bias, stride=1, relu=False):
     """3x3 / pad 1 convolution of a channels_last map on the fp32 MFMA, bias (+ReLU) fused.
     x [N, Cin, H, W] in channels_last storage; w_taps [3, 3, Cin, Cout] contiguous;
     -> [N, Cout, Ho, Wo] channels_last."""
-    lib = native.load()
-    _require(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4, 'conv3x3_nhwc: fp32 4-D')
-    _require(x.is_contiguous(memory_format=torch.channels_last), 'conv3x3_nhwc: channels_last input')
+    _nhwc(x, 'conv3x3_nhwc')
     _dev(w_taps, 'w_taps', torch.float32)
     N, Cin, H, W = x.shape
     _require(tuple(w_taps.shape[:3]) == (3, 3, Cin), 'conv3x3_nhwc: weight must be [3,3,Cin,Cout]')
     Cout = w_taps.shape[3]
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _Timed('conv3x3'):
-        st = lib.pave_conv3x3_nhwc_f32(x.data_ptr(), w_taps.data_ptr(),
-                                       bias.data_ptr() if bias is not None else None,
-                                       y.data_ptr(), N, H, W, Cin, Cout, int(stride),
-                                       int(bool(relu)), _stream_ptr())
-    native.check(st, 'conv3x3_nhwc')
+    _launch('pave_conv3x3_nhwc_f32', 'conv3x3_nhwc', x.device, x.data_ptr(), w_taps.data_ptr(), _ptr(bias),
+            y.data_ptr(), N, H, W, Cin, Cout, int(stride), int(bool(relu)), tag='conv3x3')
     return y.permute(0, 3, 1, 2)
 
 
@@ -732,7 +693,6 @@ def rows_gemm_bias_res_act(a, w_kn, bias=None, residual=None, relu=False, out=No
     A1 = relu(a + a_bias) if a_bias is given else a  (the Bottleneck tail `bn2 -> relu -> conv3 ->
     bn3 -> += identity | downsample(x) -> relu`, resnet.py:264-283).  w_kn is [K (+ K2), N].
     `residual` may be the tensor given as `out` (in-place accumulate into the identity)."""
-    lib = native.load()
     _dev(a, 'a', torch.float32)
     _dev(w_kn, 'w_kn', torch.float32)
     _require(a.dim() == 2 and w_kn.dim() == 2, 'rows_gemm: a [M,K], w [K,N]')
@@ -756,30 +716,22 @@ def rows_gemm_bias_res_act(a, w_kn, bias=None, residual=None, relu=False, out=No
     else:
         _dev(out, 'out', torch.float32)
         _require(tuple(out.shape) == (M, N), 'rows_gemm: out [M,N]')
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(a.device), _Timed('rows_gemm'):
-        st = lib.pave_rows_gemm_bias_res_act_f32(
-            a.data_ptr(), ptr(a_bias), ptr(a2), w_kn.data_ptr(), ptr(bias), ptr(residual),
-            out.data_ptr(), M, K, K2, N, int(bool(relu)), _stream_ptr())
-    native.check(st, 'rows_gemm_bias_res_act')
+    _launch('pave_rows_gemm_bias_res_act_f32', 'rows_gemm_bias_res_act', a.device,
+            a.data_ptr(), _ptr(a_bias), _ptr(a2), w_kn.data_ptr(), _ptr(bias), _ptr(residual),
+            out.data_ptr(), M, K, K2, N, int(bool(relu)), tag='rows_gemm')
     return out
 
 
 def bias_relu_maxpool_nhwc(x, bias):
     """maxpool3x3/s2/p1(relu(x + bias)) of a channels_last map in one pass (ResNet stem tail)."""
-    lib = native.load()
-    _require(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4, 'bias_relu_maxpool: fp32 4-D')
-    _require(x.is_contiguous(memory_format=torch.channels_last),
-             'bias_relu_maxpool: channels_last input')
+    _nhwc(x, 'bias_relu_maxpool')
     _dev(bias, 'bias', torch.float32)
     N, C, H, W = x.shape
     _require(bias.numel() == C, 'bias_relu_maxpool: bias [C]')
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((N, Ho, Wo, C), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _Timed('stem_pool'):
-        st = lib.pave_bias_relu_maxpool_nhwc_f32(x.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                 N, H, W, C, _stream_ptr())
-    native.check(st, 'bias_relu_maxpool_nhwc')
+    _launch('pave_bias_relu_maxpool_nhwc_f32', 'bias_relu_maxpool_nhwc', x.device,
+            x.data_ptr(), bias.data_ptr(), y.data_ptr(), N, H, W, C, tag='stem_pool')
     return y.permute(0, 3, 1, 2)
 
 
@@ -787,15 +739,11 @@ def split_bf16x3(x, planes=3):
     """fp32 tensor -> int16 tensor [planes, *x.shape] of bf16 bit patterns: truncation terms, the
     last rounded to nearest (planes = 3: x == p0 + p1 + p2 exactly).  planes = PLANES_FP16: one
     plane of fp16 bit patterns."""
-    lib = native.load()
     _dev(x, 'x', torch.float32)
     _require(planes in (1, 2, 3, PLANES_FP16), 'split_bf16x3: planes must be 1, 2, 3 or PLANES_FP16')
     n_out = 1 if planes == PLANES_FP16 else planes
     out = torch.empty((n_out,) + tuple(x.shape), dtype=torch.int16, device=x.device)
-    with torch.cuda.device(x.device):
-        st = lib.pave_split_bf16x3_f32(x.data_ptr(), out.data_ptr(), x.numel(), planes,
-                                       _stream_ptr())
-    native.check(st, 'split_bf16x3')
+    _launch('pave_split_bf16x3_f32', 'split_bf16x3', x.device, x.data_ptr(), out.data_ptr(), x.numel(), planes)
     return out.view(torch.float16) if planes == PLANES_FP16 else out
 
 
@@ -890,7 +838,6 @@ def gemm_bf16x3(a, w_planes, bias=None, residual=None, relu=False, out=None, a_b
             gemm_bf16x3(a[M1:], w_planes, bias, residual[M1:] if residual is not None else None, relu=relu,
                         out=out[M1:], fp16=fp16)
             return out
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     # few row tiles and a long K (a one-clip batch's layer4 1x1 reductions, the neck's C5 lateral): the split-K
     # form, as for the 3x3 convolutions (workspace from torch's stream-aware caching allocator)
     # (a plan exists only for K >= 2048 on fewer than 200 row tiles -- pave_internal_splitk_plan --, so the ~170
@@ -900,17 +847,18 @@ def gemm_bf16x3(a, w_planes, bias=None, residual=None, relu=False, out=None, a_b
             and relu in (False, True, 0, 1)) else 0
     if ws_bytes > 0:
         ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device), _Timed(_gemm_tag('gemm_bf16x3', M), 2 * M * K * N, (M, K, N, 'relu' if relu else '', 'res' if residual is not None else '', 'split-K')):
-            st = lib.pave_gemm_bf16x3_splitk_f32(a.data_ptr(), w_planes.data_ptr(), ptr(bias), ptr(residual),
-                                                 out.data_ptr(), M, K, N, int(bool(relu)), npl, ws.data_ptr(),
-                                                 ws_bytes, _stream_ptr())
-        native.check(st, 'gemm_bf16x3_splitk')
+        _launch('pave_gemm_bf16x3_splitk_f32', 'gemm_bf16x3_splitk', a.device,
+                a.data_ptr(), w_planes.data_ptr(), _ptr(bias), _ptr(residual),
+                out.data_ptr(), M, K, N, int(bool(relu)), npl, ws.data_ptr(), ws_bytes,
+                tag=_gemm_tag('gemm_bf16x3', M), flops=2 * M * K * N,
+                shape=(M, K, N, 'relu' if relu else '', 'res' if residual is not None else '', 'split-K'))
         return out
-    with torch.cuda.device(a.device), _Timed(_gemm_tag('gemm_bf16x3', M), 2 * M * K * N, (M, K, N, 'relu' if relu else '', 'res' if residual is not None else '', 'abias' if a_bias is not None else '')):
-        st = lib.pave_gemm_bf16x3_f32(a.data_ptr(), ptr(a_bias), w_planes.data_ptr(), ptr(bias),
-                                      ptr(residual), out.data_ptr(), M, K, N,
-                                      _ACT_CODE.get(relu, int(bool(relu))), npl, _stream_ptr())
-    native.check(st, 'gemm_bf16x3')
+    _launch('pave_gemm_bf16x3_f32', 'gemm_bf16x3', a.device,
+            a.data_ptr(), _ptr(a_bias), w_planes.data_ptr(), _ptr(bias),
+            _ptr(residual), out.data_ptr(), M, K, N, _ACT_CODE.get(relu, int(bool(relu))), npl,
+            tag=_gemm_tag('gemm_bf16x3', M), flops=2 * M * K * N,
+            shape=(M, K, N, 'relu' if relu else '', 'res' if residual is not None else '',
+                   'abias' if a_bias is not None else ''))
     return out
 
 
@@ -919,7 +867,6 @@ def gemm_bf16x3_cat(a, a2, w_planes, bias=None, residual=None, relu=False, out=N
     accumulator (the Bottleneck tail with a stride-1 downsample: conv3 and the downsample
     convolution in one launch, no concatenation copy).  w_planes = split_weight_bf16x3 of the
     [N, K1 + K2] row-concatenated weight."""
-    lib = native.load()
     _dev(a, 'a', torch.float32)
     _dev(a2, 'a2', torch.float32)
     npl = _planes(w_planes, only=_Q_PLANES)
@@ -941,12 +888,10 @@ def gemm_bf16x3_cat(a, a2, w_planes, bias=None, residual=None, relu=False, out=N
     else:
         _dev(out, 'out', torch.float32)
         _require(tuple(out.shape) == (M, N), 'gemm_bf16x3_cat: out [M, N]')
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(a.device), _Timed(_gemm_tag('gemm_bf16x3', M), 2 * M * K * N, (M, K, N, 'cat', f'k1={K1}')):
-        st = lib.pave_gemm_bf16x3_cat_f32(a.data_ptr(), K1, a2.data_ptr(), w_planes.data_ptr(),
-                                          ptr(bias), ptr(residual), out.data_ptr(), M, K, N,
-                                          int(bool(relu)), npl, _stream_ptr())
-    native.check(st, 'gemm_bf16x3_cat')
+    _launch('pave_gemm_bf16x3_cat_f32', 'gemm_bf16x3_cat', a.device,
+            a.data_ptr(), K1, a2.data_ptr(), w_planes.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(), M, K, N,
+            int(bool(relu)), npl,
+            tag=_gemm_tag('gemm_bf16x3', M), flops=2 * M * K * N, shape=(M, K, N, 'cat', f'k1={K1}'))
     return out
 
 
@@ -954,7 +899,6 @@ def gemm_bf16x3_grouped(a, w_planes, bias, group_n, relu=False):
     """Grouped row GEMM: a [M, G*K] (group i = columns [i K, (i+1) K)), w_planes = planes of the
     [G*group_n, K] row-concatenated per-group weights -> out [M, G*group_n] with
     out[:, i*group_n:(i+1)*group_n] = act(a_i @ W_i^T + bias_i).  One launch for G Linears."""
-    lib = native.load()
     _dev(a, 'a', torch.float32)
     npl = _planes(w_planes, only=_Q_PLANES)
     _require(a.dim() == 2, 'gemm_bf16x3_grouped: a [M, G*K], w_planes [K/16, 3, N, 16]')
@@ -966,12 +910,10 @@ def gemm_bf16x3_grouped(a, w_planes, bias, group_n, relu=False):
         _dev(bias, 'bias', torch.float32)
         _require(bias.numel() == N, 'gemm_bf16x3_grouped: bias [N]')
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device), _Timed(_gemm_tag('gemm_bf16x3', M), 2 * M * K * N, (M, K, N, 'grouped', f'g{G}')):
-        st = lib.pave_gemm_bf16x3_grouped_f32(a.data_ptr(), lda, w_planes.data_ptr(),
-                                              bias.data_ptr() if bias is not None else None,
-                                              out.data_ptr(), M, K, N, int(group_n), int(bool(relu)),
-                                              npl, _stream_ptr())
-    native.check(st, 'gemm_bf16x3_grouped')
+    _launch('pave_gemm_bf16x3_grouped_f32', 'gemm_bf16x3_grouped', a.device,
+            a.data_ptr(), lda, w_planes.data_ptr(), _ptr(bias), out.data_ptr(), M, K, N, int(group_n),
+            int(bool(relu)), npl,
+            tag=_gemm_tag('gemm_bf16x3', M), flops=2 * M * K * N, shape=(M, K, N, 'grouped', f'g{G}'))
     return out
 
 
@@ -979,10 +921,7 @@ def conv1x1_strided_split(x, w_planes, bias=None, stride=2, relu=False):
     """1x1 convolution with a stride on a channels_last map through the 3-plane split GEMM (the A
     rows are the strided input pixels: no slice copy).  x [N, Cin, H, W] channels_last;
     w_planes = split_weight_bf16x3(weight [Cout, Cin]) -> [N, Cout, Ho, Wo] channels_last."""
-    lib = native.load()
-    _require(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4, 'conv1x1_strided_split: fp32 4-D')
-    _require(x.is_contiguous(memory_format=torch.channels_last),
-             'conv1x1_strided_split: channels_last input')
+    _nhwc(x, 'conv1x1_strided_split')
     npl = _planes(w_planes, only=_Q_PLANES)
     N, Cin, H, W = x.shape
     _require(w_planes.shape[0] * 16 == Cin, 'conv1x1_strided_split: w_planes [Cin/16, 3, Cout, 16]')
@@ -992,11 +931,10 @@ def conv1x1_strided_split(x, w_planes, bias=None, stride=2, relu=False):
         _require(bias.numel() == Cout, 'conv1x1_strided_split: bias [Cout]')
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _Timed('conv1x1_strided', 2 * N * Ho * Wo * Cin * Cout, (N * Ho * Wo, Cin, Cout, f's{stride}')):
-        st = lib.pave_conv1x1_strided_split_f32(
-            x.data_ptr(), w_planes.data_ptr(), bias.data_ptr() if bias is not None else None,
-            y.data_ptr(), N, H, W, Cin, Cout, int(stride), int(bool(relu)), npl, _stream_ptr())
-    native.check(st, 'conv1x1_strided_split')
+    _launch('pave_conv1x1_strided_split_f32', 'conv1x1_strided_split', x.device,
+            x.data_ptr(), w_planes.data_ptr(), _ptr(bias),
+            y.data_ptr(), N, H, W, Cin, Cout, int(stride), int(bool(relu)), npl,
+            tag='conv1x1_strided', flops=2 * N * Ho * Wo * Cin * Cout, shape=(N * Ho * Wo, Cin, Cout, f's{stride}'))
     return y.permute(0, 3, 1, 2)
 
 
@@ -1004,7 +942,6 @@ def conv3x3s2_c3_nchw(x, w_taps, bias=None, relu=False):
     """HRNet stem conv1: 3x3 / stride 2 / pad 1, 3 -> 64 channels, read straight from the NCHW batch
     x [N, 3, H, W] (contiguous) -> [N, 64, Ho, Wo] channels_last; w_taps [27, 64] =
     weight.permute(1, 2, 3, 0).reshape(27, 64) (pave_conv3x3s2_c3_nchw_f32)."""
-    lib = native.load()
     _dev(x, 'x', torch.float32)
     _dev(w_taps, 'w_taps', torch.float32)
     _require(x.dim() == 4 and x.shape[1] == 3 and tuple(w_taps.shape) == (27, 64),
@@ -1015,11 +952,8 @@ def conv3x3s2_c3_nchw(x, w_taps, bias=None, relu=False):
     N, _, H, W = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((N, Ho, Wo, 64), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        st = lib.pave_conv3x3s2_c3_nchw_f32(x.data_ptr(), w_taps.data_ptr(),
-                                            bias.data_ptr() if bias is not None else None,
-                                            y.data_ptr(), N, H, W, int(bool(relu)), _stream_ptr())
-    native.check(st, 'conv3x3s2_c3_nchw')
+    _launch('pave_conv3x3s2_c3_nchw_f32', 'conv3x3s2_c3_nchw', x.device, x.data_ptr(), w_taps.data_ptr(), _ptr(bias),
+            y.data_ptr(), N, H, W, int(bool(relu)))
     return y.permute(0, 3, 1, 2)
 
 
@@ -1045,15 +979,12 @@ def repitch_rows(x):
     """x [..., W] dense fp32 -> the same rows at a pitch of roundup(W, 4) elements with zero pad columns
     (pave_repitch_rows_f32): 16-byte aligned rows for the LDS-DMA stem when W % 4 != 0 (the 750 x 1333 frames of
     the reference's PoseTrack pipeline).  Returns the padded tensor [..., roundup(W, 4)]."""
-    lib = native.load()
     _dev(x, 'x', torch.float32)
     W = x.shape[-1]
     pitch = (W + 3) // 4 * 4
     out = torch.empty(tuple(x.shape[:-1]) + (pitch,), dtype=torch.float32, device=x.device)
     rows = x.numel() // W
-    with torch.cuda.device(x.device):
-        st = lib.pave_repitch_rows_f32(x.data_ptr(), out.data_ptr(), rows, W, pitch, _stream_ptr())
-    native.check(st, 'repitch_rows')
+    _launch('pave_repitch_rows_f32', 'repitch_rows', x.device, x.data_ptr(), out.data_ptr(), rows, W, pitch)
     return out
 
 
@@ -1061,7 +992,6 @@ def conv7x7s2_nchw_split(x, w_planes, bias=None, relu=False, valid_w=None):
     """7x7 / stride 2 / pad 3 stem convolution of the NCHW image batch x [N, 3, H, W] through the
     3-plane split kernel -> [N, 64, Ho, Wo] channels_last.  valid_w: x is a `repitch_rows` result whose real
     width is valid_w (columns valid_w .. W - 1 are zero): the output is that of the valid_w-wide image."""
-    lib = native.load()
     _dev(x, 'x', torch.float32)
     npl = _planes(w_planes, only=_Q_PLANES)
     _require(x.dim() == 4 and x.shape[1] == 3, 'conv7x7s2_nchw_split: x [N, 3, H, W] (NCHW, dense)')
@@ -1075,17 +1005,15 @@ def conv7x7s2_nchw_split(x, w_planes, bias=None, relu=False, valid_w=None):
         _require(bias.numel() == Cout, 'conv7x7s2_nchw_split: bias [Cout]')
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _Timed('conv7x7_stem', 2 * N * Ho * Wo * Cout * 147, (N * Ho * Wo, 147, Cout)):
-        st = lib.pave_conv7x7s2_nchw_split_f32(
-            x.data_ptr(), w_planes.data_ptr(), bias.data_ptr() if bias is not None else None,
-            y.data_ptr(), N, H, W, pitch, Cout, int(bool(relu)), npl, _stream_ptr())
-    native.check(st, 'conv7x7s2_nchw_split')
+    _launch('pave_conv7x7s2_nchw_split_f32', 'conv7x7s2_nchw_split', x.device,
+            x.data_ptr(), w_planes.data_ptr(), _ptr(bias),
+            y.data_ptr(), N, H, W, pitch, Cout, int(bool(relu)), npl,
+            tag='conv7x7_stem', flops=2 * N * Ho * Wo * Cout * 147, shape=(N * Ho * Wo, 147, Cout))
     return y.permute(0, 3, 1, 2)
 
 
 def ref_update(tmp, ref, eps=1e-5):
     """sigmoid(tmp + inverse_sigmoid(ref)) in one launch (decoder reference-point update)."""
-    lib = native.load()
     _require(tmp.is_cuda and tmp.dtype == torch.float32 and ref.dtype == torch.float32
              and tuple(tmp.shape) == tuple(ref.shape), 'ref_update: fp32 device tensors, same shape')
     if (tmp.dim() >= 2 and not tmp.is_contiguous() and tmp.stride(-1) == 1 and ref.is_contiguous()
@@ -1095,19 +1023,15 @@ def ref_update(tmp, ref, eps=1e-5):
         # by the strided form of the same kernel (T = 1: rows [R, ld], the first o columns)
         R, o = tmp.numel() // tmp.shape[-1], tmp.shape[-1]
         out = torch.empty_like(ref)
-        with torch.cuda.device(tmp.device), _Timed('ref_update'):
-            st = lib.pave_ref_update_frames_f32(tmp.data_ptr(), ref.data_ptr(), out.data_ptr(), R, 1,
-                                                tmp.stride(-2), o, R, float(eps), _stream_ptr())
-        native.check(st, 'ref_update')
+        _launch('pave_ref_update_frames_f32', 'ref_update', tmp.device, tmp.data_ptr(), ref.data_ptr(), out.data_ptr(),
+                R, 1, tmp.stride(-2), o, R, float(eps), tag='ref_update')
         return out
     tmp, ref = tmp.contiguous(), ref.contiguous()
     out = torch.empty_like(tmp)
     if tmp.numel() == 0:
         return out
-    with torch.cuda.device(tmp.device), _Timed('ref_update'):
-        st = lib.pave_ref_update_f32(tmp.data_ptr(), ref.data_ptr(), out.data_ptr(), tmp.numel(),
-                                     float(eps), _stream_ptr())
-    native.check(st, 'ref_update')
+    _launch('pave_ref_update_f32', 'ref_update', tmp.device, tmp.data_ptr(), ref.data_ptr(), out.data_ptr(),
+            tmp.numel(), float(eps), tag='ref_update')
     return out
 
 
@@ -1115,7 +1039,6 @@ def ref_update_frames(y, ref, T, o, group, eps=1e-5, out=None):
     """sigmoid(y_t + inverse_sigmoid(ref)) read straight from the grouped per-frame MLP output
     y [R, T * op] (frame t's `o` outputs at columns [t op, t op + o)); ref [..., o] with R * T rows
     ordered (r // group, t, r % group) -> same shape as ref.  One launch, no layout copy."""
-    lib = native.load()
     _dev(y, 'y', torch.float32)
     _dev(ref, 'ref', torch.float32)
     R = y.shape[0]
@@ -1128,10 +1051,8 @@ def ref_update_frames(y, ref, T, o, group, eps=1e-5, out=None):
     else:       # (a level of the decoder's preallocated [levels, ...] stack of intermediate references)
         _dev(out, 'out', torch.float32)
         _require(tuple(out.shape) == tuple(ref.shape), 'ref_update_frames: out shaped like ref')
-    with torch.cuda.device(y.device), _Timed('ref_update'):
-        st = lib.pave_ref_update_frames_f32(y.data_ptr(), ref.data_ptr(), out.data_ptr(), R, int(T),
-                                            op, int(o), int(group), float(eps), _stream_ptr())
-    native.check(st, 'ref_update_frames')
+    _launch('pave_ref_update_frames_f32', 'ref_update_frames', y.device, y.data_ptr(), ref.data_ptr(), out.data_ptr(),
+            R, int(T), op, int(o), int(group), float(eps), tag='ref_update')
     return out
 
 
@@ -1139,7 +1060,6 @@ def groupnorm_nhwc_into(x_rows, gamma, beta, num_groups, eps, dst):
     """GroupNorm of an NHWC map given as rows x_rows [N, HW, C] (dense), written into dst
     [N, HW, C] whose batch stride may be larger than HW * C (a slice of a [N, S, C] token buffer).
     fp64 statistics in a fixed order."""
-    lib = native.load()
     _dev(x_rows, 'x', torch.float32)
     _require(x_rows.dim() == 3, 'groupnorm_nhwc_into: x [N, HW, C]')
     N, HW, C = x_rows.shape
@@ -1152,12 +1072,10 @@ def groupnorm_nhwc_into(x_rows, gamma, beta, num_groups, eps, dst):
     nchunks = max(1, min(128, (HW + 63) // 64))
     partial = torch.empty((N, nchunks, num_groups, 2), dtype=torch.float64, device=x_rows.device)
     ab = torch.empty((N, 2, C), dtype=torch.float32, device=x_rows.device)
-    with torch.cuda.device(x_rows.device), _Timed('groupnorm'):
-        st = lib.pave_groupnorm_nhwc_f32(x_rows.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                         dst.data_ptr(), dst.stride(0) if N > 1 else HW * C, N, HW,
-                                         C, int(num_groups), float(eps), partial.data_ptr(), nchunks,
-                                         ab.data_ptr(), _stream_ptr())
-    native.check(st, 'groupnorm_nhwc_into')
+    _launch('pave_groupnorm_nhwc_f32', 'groupnorm_nhwc_into', x_rows.device,
+            x_rows.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+            dst.data_ptr(), dst.stride(0) if N > 1 else HW * C, N, HW,
+            C, int(num_groups), float(eps), partial.data_ptr(), nchunks, ab.data_ptr(), tag='groupnorm')
     return dst
 
 
@@ -1165,7 +1083,6 @@ def groupnorm_levels_into(levels, num_groups):
     """GroupNorm of several NHWC maps of one N and C at once -- the neck's levels -- as three launches in all
     (statistics, scale / shift, apply) instead of three per level; per level the values of `groupnorm_nhwc_into`,
     bit for bit.  levels: [(x_rows [N, HW_l, C], gamma, beta, eps, dst [N, HW_l, C])]."""
-    lib = native.load()
     _require(len(levels) >= 1, 'groupnorm_levels_into: at least one level')
     N, _, C = levels[0][0].shape
     dev = levels[0][0].device
@@ -1190,10 +1107,9 @@ def groupnorm_levels_into(levels, num_groups):
             total_chunks += nchunks
         partial = torch.empty((N * total_chunks * num_groups * 2,), dtype=torch.float64, device=dev)
         ab = torch.empty((len(part), N, 2, C), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev), _Timed('groupnorm'):
-            st = lib.pave_groupnorm_levels_nhwc_f32(ctypes.cast(arr, ctypes.c_void_p), len(part), N, C,
-                                                    int(num_groups), partial.data_ptr(), ab.data_ptr(), _stream_ptr())
-        native.check(st, 'groupnorm_levels_into')
+        _launch('pave_groupnorm_levels_nhwc_f32', 'groupnorm_levels_into', dev,
+                ctypes.cast(arr, ctypes.c_void_p), len(part), N, C, int(num_groups), partial.data_ptr(), ab.data_ptr(),
+                tag='groupnorm')
     return [lv[4] for lv in levels]
 
 
@@ -1201,7 +1117,6 @@ def gemm_bf16x3_ln(a, w_planes, bias, residual, gamma, beta, eps, out=None):
     """out[M, 256] = LayerNorm(a @ W^T + bias + residual) * gamma + beta in ONE launch (3 bf16
     planes; the 128 x 256 block tile owns whole rows).  `residual` may be None or the tensor given
     as `out`."""
-    lib = native.load()
     _dev(a, 'a', torch.float32)
     npl = _planes(w_planes, only=_Q_PLANES)
     _require(a.dim() == 2 and w_planes.shape[0] * 16 == a.shape[1],
@@ -1231,12 +1146,11 @@ def gemm_bf16x3_ln(a, w_planes, bias, residual, gamma, beta, eps, out=None):
         gemm_bf16x3_ln(a[M1:], w_planes, bias, residual[M1:] if residual is not None else None, gamma, beta, eps,
                        out=out[M1:])
         return out
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(a.device), _Timed(_gemm_tag('gemm_bf16x3_ln', M), 2 * M * K * N, (M, K, N, 'ln', 'res' if residual is not None else '')):
-        st = lib.pave_gemm_bf16x3_ln_f32(a.data_ptr(), w_planes.data_ptr(), ptr(bias), ptr(residual),
-                                         gamma.data_ptr(), beta.data_ptr(), float(eps),
-                                         out.data_ptr(), M, K, N, npl, _stream_ptr())
-    native.check(st, 'gemm_bf16x3_ln')
+    _launch('pave_gemm_bf16x3_ln_f32', 'gemm_bf16x3_ln', a.device,
+            a.data_ptr(), w_planes.data_ptr(), _ptr(bias), _ptr(residual),
+            gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), M, K, N, npl,
+            tag=_gemm_tag('gemm_bf16x3_ln', M), flops=2 * M * K * N,
+            shape=(M, K, N, 'ln', 'res' if residual is not None else ''))
     return out
 
 
@@ -1246,7 +1160,6 @@ def gemm_fp16_act(a, w_plane, bias=None, relu=False, out_half=False, residual=No
     ln = None: act(a W^T + bias) -> [M, N] fp32, or float16 with out_half (an activation that only feeds the next
     GEMM).  ln = (gamma, beta, eps): LayerNorm(a W^T + bias + residual) gamma + beta -> [M, 256] fp32 (`residual`
     may be the tensor given as `out`)."""
-    lib = native.load()
     _require(isinstance(a, torch.Tensor) and a.is_cuda and a.is_contiguous() and a.dim() == 2
              and a.dtype in (torch.float32, torch.float16), 'gemm_fp16_act: a [M, K] fp32 or float16 on the device')
     _require(_planes(w_plane) == PLANES_FP16, 'gemm_fp16_act: one fp16 plane (split_weight_bf16x3(w, PLANES_FP16))')
@@ -1256,7 +1169,6 @@ def gemm_fp16_act(a, w_plane, bias=None, relu=False, out_half=False, residual=No
     if bias is not None:
         _dev(bias, 'bias', torch.float32)
         _require(bias.numel() == N, 'gemm_fp16_act: bias [N]')
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     if ln is not None:
         gamma, beta, eps = ln
         _dev(gamma, 'gamma', torch.float32)
@@ -1269,7 +1181,7 @@ def gemm_fp16_act(a, w_plane, bias=None, relu=False, out_half=False, residual=No
         if out is None:
             out = torch.empty((M, N), dtype=torch.float32, device=a.device)
         _require(out.dtype == torch.float32 and tuple(out.shape) == (M, N) and out.is_contiguous(), 'gemm_fp16_act: out')
-        args = (ptr(residual), gamma.data_ptr(), beta.data_ptr(), float(eps))
+        args = (_ptr(residual), gamma.data_ptr(), beta.data_ptr(), float(eps))
         tag = _gemm_tag('gemm_bf16x3_ln', M)
     else:
         _require(residual is None and out is None, 'gemm_fp16_act: the plain form takes bias + activation only')
@@ -1278,11 +1190,10 @@ def gemm_fp16_act(a, w_plane, bias=None, relu=False, out_half=False, residual=No
         tag = _gemm_tag('gemm_bf16x3', M)
     note = (M, K, N, 'f16act', 'a16' if a.dtype == torch.float16 else '', 'o16' if out_half else '',
             'ln' if ln is not None else ('relu' if relu else ''), 'res' if residual is not None else '')
-    with torch.cuda.device(a.device), _Timed(tag, 2 * M * K * N, note):
-        st = lib.pave_gemm_fp16_act_f32(a.data_ptr(), int(a.dtype == torch.float16), w_plane.data_ptr(), ptr(bias),
-                                        *args, out.data_ptr(), int(bool(out_half)), M, K, N,
-                                        2 if relu == 'gelu' else int(bool(relu)), _stream_ptr())
-    native.check(st, 'gemm_fp16_act')
+    _launch('pave_gemm_fp16_act_f32', 'gemm_fp16_act', a.device,
+            a.data_ptr(), int(a.dtype == torch.float16), w_plane.data_ptr(), _ptr(bias),
+            *args, out.data_ptr(), int(bool(out_half)), M, K, N, 2 if relu == 'gelu' else int(bool(relu)),
+            tag=tag, flops=2 * M * K * N, shape=note)
     return out
 
 
@@ -1291,7 +1202,6 @@ def gemm_bf16x3_ex(a, w_planes, bias=None, residual=None, residual_rows=0, n_spl
     """gemm_bf16x3 with a row-periodic residual table (`residual` [residual_rows, N], row m adds
     residual[m % residual_rows]) and / or the output cut at column `n_split` into two dense
     matrices -> out [M, n_split], out2 [M, N - n_split] (n_split = 0: one output, out2 = None)."""
-    lib = native.load()
     _dev(a, 'a', torch.float32)
     npl = _planes(w_planes, fp16=fp16)
     _require(a.dim() == 2 and w_planes.shape[1] in (1, 2, 3) and w_planes.shape[0] * 16 == a.shape[1],
@@ -1328,12 +1238,11 @@ def gemm_bf16x3_ex(a, w_planes, bias=None, residual=None, residual_rows=0, n_spl
     else:
         out = torch.empty((M, n_split or N), dtype=torch.float32, device=a.device)
         out2 = torch.empty((M, N - n_split), dtype=torch.float32, device=a.device) if n_split else None
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(a.device), _Timed(_gemm_tag('gemm_bf16x3', M), 2 * M * K * N, (M, K, N, 'ex', f'rows{rr}', f'split{n_split}')):
-        st = lib.pave_gemm_bf16x3_ex_f32(a.data_ptr(), ptr(a_bias), w_planes.data_ptr(), ptr(bias),
-                                         ptr(residual), rr, out.data_ptr(), ptr(out2), n_split,
-                                         M, K, N, int(bool(relu)), npl, _stream_ptr())
-    native.check(st, 'gemm_bf16x3_ex')
+    _launch('pave_gemm_bf16x3_ex_f32', 'gemm_bf16x3_ex', a.device,
+            a.data_ptr(), _ptr(a_bias), w_planes.data_ptr(), _ptr(bias),
+            _ptr(residual), rr, out.data_ptr(), _ptr(out2), n_split, M, K, N, int(bool(relu)), npl,
+            tag=_gemm_tag('gemm_bf16x3', M), flops=2 * M * K * N,
+            shape=(M, K, N, 'ex', f'rows{rr}', f'split{n_split}'))
     return out, out2
 
 
@@ -1341,7 +1250,6 @@ def swin_window_attn(qkv, bias_t, pad_qkv, heads, window, shift, scale):
     """The (shifted-)window attention core of a Swin block on the un-partitioned token map
     (pave_swin_window_attn_f32): qkv [B, H, W, 3C], bias_t [heads, ws^2, ws^2] (relative-position bias, key-major),
     pad_qkv [3C] (the qkv Linear's bias) -> [B, H, W, C]."""
-    lib = native.load()
     for t, nm in ((qkv, 'qkv'), (bias_t, 'bias_t'), (pad_qkv, 'pad_qkv')):
         _dev(t, nm, torch.float32)
     _require(qkv.dim() == 4 and qkv.shape[3] % 3 == 0, 'swin_window_attn: qkv [B, H, W, 3C]')
@@ -1351,26 +1259,21 @@ def swin_window_attn(qkv, bias_t, pad_qkv, heads, window, shift, scale):
     _require(tuple(bias_t.shape) == (heads, n, n) and pad_qkv.numel() == C3 and C == heads * 32,
              'swin_window_attn: bias_t [heads, ws^2, ws^2], pad_qkv [3C], head dim 32')
     out = torch.empty((B, H, W, C), dtype=torch.float32, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        st = lib.pave_swin_window_attn_f32(qkv.data_ptr(), bias_t.data_ptr(), pad_qkv.data_ptr(), out.data_ptr(),
-                                           B, H, W, C, int(heads), int(window), int(shift), float(scale),
-                                           _stream_ptr())
-    native.check(st, 'swin_window_attn')
+    _launch('pave_swin_window_attn_f32', 'swin_window_attn', qkv.device,
+            qkv.data_ptr(), bias_t.data_ptr(), pad_qkv.data_ptr(), out.data_ptr(),
+            B, H, W, C, int(heads), int(window), int(shift), float(scale))
     return out
 
 
 def merge_softmax_partials(parts, C, H):
     """parts [G, U, C + 2 H] (all-gathered partial rows | per-head max | per-head sum-exp) -> [U, C]: the
     exact full-softmax row (pave_merge_softmax_partials_f32), one launch."""
-    lib = native.load()
     _dev(parts, 'parts', torch.float32)
     _require(parts.dim() == 3 and parts.shape[2] == C + 2 * H, 'merge_softmax_partials: parts [G, U, C + 2 H]')
     G, U = parts.shape[0], parts.shape[1]
     out = torch.empty((U, C), dtype=torch.float32, device=parts.device)
-    with torch.cuda.device(parts.device):
-        st = lib.pave_merge_softmax_partials_f32(parts.data_ptr(), out.data_ptr(), G, U, int(C), int(H),
-                                                 _stream_ptr())
-    native.check(st, 'merge_softmax_partials')
+    _launch('pave_merge_softmax_partials_f32', 'merge_softmax_partials', parts.device,
+            parts.data_ptr(), out.data_ptr(), G, U, int(C), int(H))
     return out
 
 
@@ -1378,16 +1281,13 @@ def mha_core(qkv, n_seq, seq_len, num_heads):
     """Scaled-dot-product core of the decoders' self-attention: qkv [n_seq * seq_len, >= 3 * E]
     (q | k | v columns, E = num_heads * 32; row = (sequence, position)) -> [n_seq * seq_len, E] =
     softmax(q k^T / sqrt(32)) v per (sequence, head).  pave_mha_core_f32 (csrc/pave_decoder.hip)."""
-    lib = native.load()
     _dev(qkv, 'qkv', torch.float32)
     E = int(num_heads) * 32
     _require(qkv.dim() == 2 and qkv.shape[0] == n_seq * seq_len and qkv.shape[1] >= 3 * E,
              'mha_core: qkv [n_seq * seq_len, >= 3 * num_heads * 32]')
     out = torch.empty((qkv.shape[0], E), dtype=torch.float32, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        st = lib.pave_mha_core_f32(qkv.data_ptr(), out.data_ptr(), int(n_seq), int(seq_len),
-                                   int(num_heads), qkv.stride(0), _stream_ptr())
-    native.check(st, 'mha_core')
+    _launch('pave_mha_core_f32', 'mha_core', qkv.device, qkv.data_ptr(), out.data_ptr(), int(n_seq), int(seq_len),
+            int(num_heads), qkv.stride(0))
     return out
 
 
@@ -1395,7 +1295,6 @@ def topk_rows(x, k):
     """torch.topk(x, k, dim=1) for a 2-D fp32 device tensor as ONE launch (pave_topk_rows_f32):
     -> (values [rows, k], indices [rows, k] int64), sorted by value descending, ties by the
     lower index.  x may be any strided 2-D view (no copy)."""
-    lib = native.load()
     _require(isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
              and x.shape[0] > 0 and x.stride(1) > 0 and (x.shape[0] == 1 or x.stride(0) > 0),
              'topk_rows: x [rows, n] fp32 on the device, positive strides')
@@ -1404,17 +1303,14 @@ def topk_rows(x, k):
     _require(0 < k <= n and n <= 32768 and k <= 1024, 'topk_rows: 0 < k <= n <= 32768, k <= 1024')
     values = torch.empty((rows, k), dtype=torch.float32, device=x.device)
     index = torch.empty((rows, k), dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        st = lib.pave_topk_rows_f32(x.data_ptr(), values.data_ptr(), index.data_ptr(), rows, n,
-                                    x.stride(0), x.stride(1), k, _stream_ptr())
-    native.check(st, 'topk_rows')
+    _launch('pave_topk_rows_f32', 'topk_rows', x.device, x.data_ptr(), values.data_ptr(), index.data_ptr(), rows, n,
+            x.stride(0), x.stride(1), k)
     return values, index
 
 
 def gather_frame_poses(poses, index, T):
     """poses [B, T*Q, C] (frame-major rows), index [B, N] int64 -> [T, B*N, C]: the selected
     queries of every frame, frame-major (pave_gather_frame_poses_f32)."""
-    lib = native.load()
     _dev(poses, 'poses', torch.float32)
     _dev(index, 'index', torch.int64)
     _require(poses.dim() == 3 and poses.shape[1] % T == 0 and index.dim() == 2
@@ -1422,10 +1318,8 @@ def gather_frame_poses(poses, index, T):
     B, TQ, C = poses.shape
     N = index.shape[1]
     out = torch.empty((T, B * N, C), dtype=torch.float32, device=poses.device)
-    with torch.cuda.device(poses.device):
-        st = lib.pave_gather_frame_poses_f32(poses.data_ptr(), index.data_ptr(), out.data_ptr(), B,
-                                             int(T), TQ // T, N, C, _stream_ptr())
-    native.check(st, 'gather_frame_poses')
+    _launch('pave_gather_frame_poses_f32', 'gather_frame_poses', poses.device,
+            poses.data_ptr(), index.data_ptr(), out.data_ptr(), B, int(T), TQ // T, N, C)
     return out
 
 
@@ -1433,7 +1327,6 @@ def gather_rows_add(src, index, add=None):
     """src [n, S, C] fp32 (rows dense, any batch stride), index [n, Q] int64 -> rows [n, Q, C] = src[b, index[b, q]]
     and, with add [Q, C], (rows, rows + add): the proposal top-k's `tgt` and `query = tgt + query`
     (OT:21386, 21417) in one launch -- pave_gather_rows_add_f32."""
-    lib = native.load()
     _require(src.is_cuda and src.dtype == torch.float32 and src.dim() == 3 and src.stride(2) == 1
              and src.stride(1) == src.shape[2], 'gather_rows_add: src [n, S, C] fp32 on the device, dense rows')
     _dev(index, 'index', torch.int64)
@@ -1446,12 +1339,9 @@ def gather_rows_add(src, index, add=None):
         _dev(add, 'add', torch.float32)
         _require(tuple(add.shape) == (Q, C), 'gather_rows_add: add [Q, C]')
         total = torch.empty_like(rows)
-    with torch.cuda.device(src.device):
-        st = lib.pave_gather_rows_add_f32(src.data_ptr(), src.stride(0) if n > 1 else 0, index.data_ptr(),
-                                          add.data_ptr() if add is not None else None, rows.data_ptr(),
-                                          total.data_ptr() if total is not None else None, n, Q, S, C,
-                                          _stream_ptr())
-    native.check(st, 'gather_rows_add')
+    _launch('pave_gather_rows_add_f32', 'gather_rows_add', src.device,
+            src.data_ptr(), src.stride(0) if n > 1 else 0, index.data_ptr(), _ptr(add), rows.data_ptr(),
+            _ptr(total), n, Q, S, C)
     return rows if add is None else (rows, total)
 
 
@@ -1459,7 +1349,6 @@ def proposal_refs_(kpt, props, index, T):
     """kpt [n, Q, 2K] fp32 (unit column stride; a column slice of a padded matrix is fine), in place:
     kpt[..., 0::2] += props[b, index, 0], kpt[..., 1::2] += props[b, index, 1] (props [n or 1, S, 2]); returns
     refs [n, T*Q, 2K] = sigmoid(kpt) repeated for the T frames (OT:21390-21391, 21412) -- pave_proposal_refs_f32."""
-    lib = native.load()
     _require(kpt.is_cuda and kpt.dtype == torch.float32 and kpt.dim() == 3 and kpt.stride(2) == 1
              and kpt.stride(0) == kpt.shape[1] * kpt.stride(1), 'proposal_refs_: kpt [n, Q, 2K] fp32, rows evenly strided')
     _dev(index, 'index', torch.int64)
@@ -1468,11 +1357,10 @@ def proposal_refs_(kpt, props, index, T):
              and props.shape[0] in (1, n) and props[0].is_contiguous(), 'proposal_refs_: props [n | 1, S, 2] fp32')
     _require(tuple(index.shape) == (n, Q), 'proposal_refs_: index [n, Q]')
     refs = torch.empty((n, int(T) * Q, K2), dtype=torch.float32, device=kpt.device)
-    with torch.cuda.device(kpt.device):
-        st = lib.pave_proposal_refs_f32(kpt.data_ptr(), kpt.stride(1), props.data_ptr(),
-                                        props.stride(0) if props.shape[0] > 1 else 0, index.data_ptr(),
-                                        refs.data_ptr(), n, Q, props.shape[1], K2, int(T), _stream_ptr())
-    native.check(st, 'proposal_refs_')
+    _launch('pave_proposal_refs_f32', 'proposal_refs_', kpt.device,
+            kpt.data_ptr(), kpt.stride(1), props.data_ptr(),
+            props.stride(0) if props.shape[0] > 1 else 0, index.data_ptr(),
+            refs.data_ptr(), n, Q, props.shape[1], K2, int(T))
     return refs
 
 
@@ -1480,7 +1368,6 @@ def pose_finalize(kpts, sigmas, scores, wh, sf=None):
     """Post-processing of the refined poses (HEAD:1440-1490 + get_p) in one launch:
     kpts, sigmas [B, N, K, 2], scores [B, N], wh [B, 2] (image w, h), sf [B, 2] or None (rescale)
     -> (det_kpts [B, N, K, 3], det_bboxes [B, N, 5])."""
-    lib = native.load()
     for t, nm in ((kpts, 'kpts'), (scores, 'scores'), (wh, 'wh')):
         _dev(t, nm, torch.float32)
     # sigmas: dense, or evenly strided (x, y) rows -- a 2-column slice of the sigma branch's padded output
@@ -1498,12 +1385,9 @@ def pose_finalize(kpts, sigmas, scores, wh, sf=None):
         _require(sf.numel() == 2 * B, 'pose_finalize: sf [B, 2]')
     det_kpts = torch.empty((B, N, K, 3), dtype=torch.float32, device=kpts.device)
     det_bboxes = torch.empty((B, N, 5), dtype=torch.float32, device=kpts.device)
-    with torch.cuda.device(kpts.device):
-        st = lib.pave_pose_finalize_f32(kpts.data_ptr(), sigmas.data_ptr(), scores.data_ptr(),
-                                        wh.data_ptr(), sf.data_ptr() if sf is not None else None,
-                                        det_kpts.data_ptr(), det_bboxes.data_ptr(), B, N, K,
-                                        int(sf is not None), sigma_ld, _stream_ptr())
-    native.check(st, 'pose_finalize')
+    _launch('pave_pose_finalize_f32', 'pose_finalize', kpts.device,
+            kpts.data_ptr(), sigmas.data_ptr(), scores.data_ptr(), wh.data_ptr(), _ptr(sf),
+            det_kpts.data_ptr(), det_bboxes.data_ptr(), B, N, K, int(sf is not None), sigma_ld)
     return det_kpts, det_bboxes
 
 
@@ -1527,7 +1411,6 @@ def bottleneck_chain(c1, w2_planes, b2, w3_planes, b3, residual=None, a2=None, w
     with w3_planes = the planes of the [256, 64 + k2] concatenated weight.
     c1 = w2_planes = None with c2 [N, 64, H, W] channels_last given: the launch starts at conv3
     (the 3x3 was run by conv3x3_split)."""
-    lib = native.load()
     tail_only = c1 is None
     src = c2 if tail_only else c1
     _require(src is not None and src.is_cuda and src.dtype == torch.float32 and src.dim() == 4
@@ -1573,15 +1456,12 @@ def bottleneck_chain(c1, w2_planes, b2, w3_planes, b3, residual=None, a2=None, w
     if not tail_only:
         c2 = torch.empty((M, 64), dtype=torch.float32, device=src.device)
     c1n = torch.empty((N, H, W, cn), dtype=torch.float32, device=src.device) if cn else None
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     flops = 2 * M * ((0 if tail_only else 576 * 64) + (64 + k2) * 256 + 256 * cn)
-    with torch.cuda.device(src.device), _Timed('bottleneck_chain', flops,
-                                               (M, 64, 256, cn, f'k2={k2}', 'tail' if tail_only else '')):
-        st = lib.pave_bottleneck_chain_f32(
-            ptr(c1), ptr(w2_planes), ptr(b2), c2.data_ptr(), w3_planes.data_ptr(), ptr(b3),
-            ptr(residual), ptr(a2), k2, out.data_ptr(), ptr(w1n_planes), ptr(b1n), ptr(c1n), cn,
-            N, H, W, npl, _stream_ptr())
-    native.check(st, 'bottleneck_chain')
+    _launch('pave_bottleneck_chain_f32', 'bottleneck_chain', src.device,
+            _ptr(c1), _ptr(w2_planes), _ptr(b2), c2.data_ptr(), w3_planes.data_ptr(), _ptr(b3),
+            _ptr(residual), _ptr(a2), k2, out.data_ptr(), _ptr(w1n_planes), _ptr(b1n), _ptr(c1n), cn,
+            N, H, W, npl,
+            tag='bottleneck_chain', flops=flops, shape=(M, 64, 256, cn, f'k2={k2}', 'tail' if tail_only else ''))
     return out, (c1n.permute(0, 3, 1, 2) if cn else None)
 
 
@@ -1592,8 +1472,7 @@ def conv3x3_split(x, w_planes, bias=None, stride=1, relu=False, fp16=False, resi
     output channels when the planes were zero-padded (3 planes: Cin % 16 == 0, Cout % 4 == 0);
     residual [N, Cout, Ho, Wo] channels_last is added before the ReLU (3 planes)."""
     lib = native.load()
-    _require(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4, 'conv3x3_split: fp32 4-D')
-    _require(x.is_contiguous(memory_format=torch.channels_last), 'conv3x3_split: channels_last input')
+    _nhwc(x, 'conv3x3_split')
     npl = _planes(w_planes, fp16=fp16)
     N, Cin, H, W = x.shape
     kp = 9 * Cin if npl not in _Q_PLANES else (9 * Cin + 31) // 32 * 32
@@ -1617,19 +1496,15 @@ def conv3x3_split(x, w_planes, bias=None, stride=1, relu=False, fp16=False, resi
         if npl in _Q_PLANES else 0
     if ws_bytes > 0:
         ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device), _Timed('conv3x3_split', 2 * N * Ho * Wo * Cout * 9 * Cin,
-                                                 (N * Ho * Wo, 9 * Cin, Cout, f'3x3 s{stride} split-K', 'res' if residual is not None else '')):
-            st = lib.pave_conv3x3_splitk_f32(
-                x.data_ptr(), w_planes.data_ptr(), bias.data_ptr() if bias is not None else None,
-                residual.data_ptr() if residual is not None else None,
-                y.data_ptr(), N, H, W, Cin, Cout, int(stride), int(bool(relu)), ws.data_ptr(), ws_bytes,
-                npl, _stream_ptr())
-        native.check(st, 'conv3x3_splitk')
+        _launch('pave_conv3x3_splitk_f32', 'conv3x3_splitk', x.device,
+                x.data_ptr(), w_planes.data_ptr(), _ptr(bias), _ptr(residual),
+                y.data_ptr(), N, H, W, Cin, Cout, int(stride), int(bool(relu)), ws.data_ptr(), ws_bytes, npl,
+                tag='conv3x3_split', flops=2 * N * Ho * Wo * Cout * 9 * Cin,
+                shape=(N * Ho * Wo, 9 * Cin, Cout, f'3x3 s{stride} split-K', 'res' if residual is not None else ''))
         return y.permute(0, 3, 1, 2)
-    with torch.cuda.device(x.device), _Timed('conv3x3_split', 2 * N * Ho * Wo * Cout * 9 * Cin, (N * Ho * Wo, 9 * Cin, Cout, f'3x3 s{stride}', 'res' if residual is not None else '')):
-        st = lib.pave_conv3x3_split_f32(
-            x.data_ptr(), w_planes.data_ptr(), bias.data_ptr() if bias is not None else None,
-            residual.data_ptr() if residual is not None else None,
-            y.data_ptr(), N, H, W, Cin, Cout, int(stride), int(bool(relu)), npl, _stream_ptr())
-    native.check(st, 'conv3x3_split')
+    _launch('pave_conv3x3_split_f32', 'conv3x3_split', x.device,
+            x.data_ptr(), w_planes.data_ptr(), _ptr(bias), _ptr(residual),
+            y.data_ptr(), N, H, W, Cin, Cout, int(stride), int(bool(relu)), npl,
+            tag='conv3x3_split', flops=2 * N * Ho * Wo * Cout * 9 * Cin,
+            shape=(N * Ho * Wo, 9 * Cin, Cout, f'3x3 s{stride}', 'res' if residual is not None else ''))
     return y.permute(0, 3, 1, 2)

@@ -12,8 +12,7 @@ import ctypes
 
 import torch
 
-from . import native
-from .ops import _require, _stream_ptr
+from .ops import _launch, _require
 
 MEAN = (123.675, 116.28, 103.53)
 STD = (58.395, 57.12, 57.375)
@@ -45,7 +44,6 @@ def preprocess_clip(frames, img_scale=(1333, 800), size_divisor=1, mean=MEAN, st
 
     flip=True: mmdet's RandomFlip(horizontal) between Resize and Normalize -- the resized image is mirrored
     within its Wn columns (pave_preprocess_frames_flip), the padding stays on the right."""
-    lib = native.load()
     _require(frames.is_cuda and frames.dim() == 4 and frames.shape[-1] == 3 and
              frames.is_contiguous(), 'preprocess_clip: frames must be a contiguous device '
              '[T, H, W, 3] tensor')
@@ -55,12 +53,9 @@ def preprocess_clip(frames, img_scale=(1333, 800), size_divisor=1, mean=MEAN, st
     out = torch.empty((1, T, 3, Hp, Wp), dtype=torch.float32, device=frames.device)
     m = (ctypes.c_float * 3)(*mean)
     s = (ctypes.c_float * 3)(*std)
-    with torch.cuda.device(frames.device):
-        fn = lib.pave_preprocess_frames_flip if flip else lib.pave_preprocess_frames
-        st = fn(frames.data_ptr(), int(frames.dtype == torch.uint8), out.data_ptr(), T, H0, W0, Hn, Wn, Hp, Wp,
-                ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), int(bool(to_rgb)),
-                _stream_ptr())
-    native.check(st, 'preprocess_frames')
+    _launch('pave_preprocess_frames_flip' if flip else 'pave_preprocess_frames', 'preprocess_frames', frames.device,
+            frames.data_ptr(), int(frames.dtype == torch.uint8), out.data_ptr(), T, H0, W0, Hn, Wn, Hp, Wp,
+            ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), int(bool(to_rgb)))
     meta = dict(ori_shape=(H0, W0, 3), img_shape=(Hn, Wn, 3), pad_shape=(Hp, Wp, 3),
                 batch_input_shape=(Hp, Wp), scale_factor=scale_factor, flip=bool(flip),
                 flip_direction='horizontal' if flip else None)

@@ -26,6 +26,56 @@ def test_capi_exports_every_declared_symbol():
     assert lib.pave_abi_version() == int(m.group(1)) == native.ABI_VERSION
 
 
+def test_binding_is_derived_from_the_header():
+    """native.py types every entry point from include/pave_hip.h (no hand-kept argument lists): the parser on a
+    header text written here, its refusal to guess, and the types the loaded library carries."""
+    from pavenet_amd import native
+    from pavenet_amd.build_native import build_native
+    vp, ci, ll, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double
+    text = ('#ifndef X_H_\n#define X_H_\n#include <stdint.h>\n'
+            '#define PAVE_E_ARG (-1)   /* bad argument */\n#define PAVE_ABI_VERSION 7\n#define PAVE_NAME "x"\n'
+            '/* int pave_hidden(size_t n); -- and a call in prose: pave_prose(1) */\n'
+            'typedef struct pave_thing { const float* x; int n; } pave_thing;\n'
+            'int pave_version(void);\n'
+            'const char* pave_message(void);\n'
+            'long long pave_bytes(long long M, int K);\n'
+            'int pave_launch(const pave_thing* things, const int64_t* index, long long rows,\n'
+            '                float eps, double thresh,   // a line comment with pave_other(\n'
+            '                const int n, void* stream);\n'
+            '#endif\n')
+    functions, defines = native.parse_header(text)
+    assert functions == {'pave_version': (ci, []), 'pave_message': (ctypes.c_char_p, []),
+                         'pave_bytes': (ll, [ll, ci]), 'pave_launch': (ci, [vp, vp, ll, cf, cd, ci, vp])}
+    assert list(functions) == ['pave_version', 'pave_message', 'pave_bytes', 'pave_launch']
+    assert defines == {'PAVE_E_ARG': -1, 'PAVE_ABI_VERSION': 7}
+    # nothing is guessed: an unknown scalar, a struct by value, an array, a function pointer, a definition
+    for bad, named in (('int pave_a(const float* x, size_t n, void* stream);', 'size_t n'),
+                       ('int pave_b(pave_thing thing, void* stream);', 'pave_thing thing'),
+                       ('int pave_c(int hw[8], void* stream);', 'hw'),
+                       ('unsigned pave_d(int n);', 'pave_d'),
+                       ('int pave_e(void (*done)(int), void* stream);', 'pave_e'),
+                       ('static inline int pave_f(int n) { return n; }', 'pave_f'),
+                       ('int pave_g(int n)\n', 'pave_g')):
+        with pytest.raises(native.NativeLibraryError, match=re.escape(named)):
+            native.parse_header('int pave_ok(int n);\n' + bad + '\n')
+    # the real header: every declaration typed, and the loaded library carries exactly those types
+    build_native()
+    lib = native.load()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    functions, defines = native.parse_header(open(os.path.join(root, 'include', 'pave_hip.h')).read())
+    assert tuple(functions) == native.EXPORTED and len(functions) >= 55
+    assert set(native.SIGNATURES) < set(native.EXPORTED)
+    for name in native.EXPORTED:
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == functions[name][1], name
+        assert fn.restype is functions[name][0], name
+    assert lib.pave_last_error.restype is ctypes.c_char_p and lib.pave_gemm_splitk_workspace_bytes.restype is ll
+    assert lib.pave_gemm_splitk_workspace_bytes.argtypes == [ll, ci, ci]
+    assert lib.pave_oks_nms_f32.argtypes == [vp, vp, vp, cd, vp, vp, ci, ci, ci, vp]
+    assert native.ABI_VERSION == defines['PAVE_ABI_VERSION'] and defines['PAVE_E_ARG'] == -1
+    assert (native.AUG_MAX_AUGS, native.AUG_MAX_SLOTS, native.AUG_MAX_K) == (16, 128, 64)
+
+
 def test_ctypes_struct_layout_equals_the_header(tmp_path):
     """`native.GnLevel` is passed to pave_groupnorm_levels_nhwc_f32 as an array of the header's `pave_gn_level`: a
     field that drifts apart corrupts device pointers silently.  The header is compiled (gcc, as C) into a program
