@@ -416,19 +416,10 @@ int pave_aug_merge_nms_f32(const pave_aug_plan* plan, float score_thr, int max_n
   int threads = ((total + kMaxPerThread - 1) / kMaxPerThread + 63) / 64 * 64;
   threads = threads < 64 ? 64 : (threads > 1024 ? 1024 : threads);
   const size_t smem = (size_t)total * 9 * 4 + 16 * 4 * 3;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(aug_merge_nms_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "aug_merge_nms: cannot raise the dynamic LDS limit");
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(aug_merge_nms_kernel, dim3((unsigned)B), dim3(threads), smem,
-                     reinterpret_cast<hipStream_t>(stream), *plan, score_thr, max_num, M, method, iou_thr, sigma,
-                     min_score, offset, dets, labels, kpts, inds, keep, count);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch_lds<aug_merge_nms_kernel>(
+      "aug_merge_nms: cannot raise the dynamic LDS limit", dim3((unsigned)B), dim3(threads), smem,
+      reinterpret_cast<hipStream_t>(stream), *plan, score_thr, max_num, M, method, iou_thr, sigma, min_score, offset,
+      dets, labels, kpts, inds, keep, count);
 }
 
 int pave_hflip_canvas_f32(const float* x, float* y, const int32_t* valid_w, int valid_w_all, int n, int C, int Hp,
@@ -439,11 +430,9 @@ int pave_hflip_canvas_f32(const float* x, float* y, const int32_t* valid_w, int 
   const long long total = (long long)n * C * Hp * Wp;
   long long nb = (total + 255) / 256;
   if (nb > 256 * 32) nb = 256 * 32;
-  hipLaunchKernelGGL(hflip_canvas_kernel, dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     x, y, valid_w, valid_w_all, C, Hp, Wp, total);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<hflip_canvas_kernel>(
+      dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, y, valid_w, valid_w_all, C, Hp, Wp,
+      total);
 }
 
 }  // extern "C"

@@ -188,20 +188,10 @@ __global__ __launch_bounds__(NW * 64) void mha_core_kernel(const MhaParams p) {
 template <int NW, int LQ>
 int launch_mha(const MhaParams& p, int n_seq, hipStream_t st) {
   const size_t smem = (size_t)2 * p.L * kPad * sizeof(float);
-  auto kern = mha_core_kernel<NW, LQ>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "mha_core: cannot raise the dynamic LDS limit");
-    attr_set = true;
-  }
   constexpr int QB = NW * (64 / LQ);   // queries per workgroup
   const dim3 grid((unsigned)((p.L + QB - 1) / QB), (unsigned)p.H, (unsigned)n_seq);
-  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, st, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch_lds<mha_core_kernel<NW, LQ>>("mha_core: cannot raise the dynamic LDS limit", grid, dim3(NW * 64),
+                                                  smem, st, p);
 }
 
 }  // namespace
@@ -384,19 +374,9 @@ extern "C" int pave_topk_rows_f32(const float* x, float* values, long long* inde
   if (n > kTopkMaxN || k > kTopkMaxK)
     return pave_internal_fail(PAVE_E_UNSUPPORTED, "topk_rows: n <= 32768 and k <= 1024");
   const size_t smem = (size_t)((n + 1) & ~1) * 4 + (size_t)kTopkMaxK * 8;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_rows_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "topk_rows: cannot raise the dynamic LDS limit");
-    attr_set = true;
-  }
   TopkParams p{x, values, index, n, k, ld, cs};
-  hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)rows), dim3(kTopkThreads), smem,
-                     reinterpret_cast<hipStream_t>(stream), p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch_lds<topk_rows_kernel>("topk_rows: cannot raise the dynamic LDS limit", dim3((unsigned)rows),
+                                           dim3(kTopkThreads), smem, reinterpret_cast<hipStream_t>(stream), p);
 }
 
 // ---------------------------------------------------------------------------
@@ -485,11 +465,8 @@ extern "C" int pave_gather_frame_poses_f32(const float* poses, const long long* 
     return pave_internal_fail(PAVE_E_ARG, "gather_frame_poses: sizes must be positive");
   const long long total = (long long)T * B * N * C;
   const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(gather_frame_poses_kernel, dim3(blocks), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), poses, index, out, B, T, Q, N, C);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<gather_frame_poses_kernel>(
+      dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), poses, index, out, B, T, Q, N, C);
 }
 
 extern "C" int pave_pose_finalize_f32(const float* kpts, const float* sigmas, const float* scores,
@@ -500,12 +477,9 @@ extern "C" int pave_pose_finalize_f32(const float* kpts, const float* sigmas, co
     return pave_internal_fail(PAVE_E_ARG, "pose_finalize: null pointer");
   if (B <= 0 || N <= 0 || K <= 0 || K > 64 || sigma_ld < 2)
     return pave_internal_fail(PAVE_E_ARG, "pose_finalize: B, N > 0, 0 < K <= 64, sigma_ld >= 2");
-  hipLaunchKernelGGL(pose_finalize_kernel, dim3((unsigned)(B * N)), dim3(64), 0,
-                     reinterpret_cast<hipStream_t>(stream), kpts, sigmas, scores, wh, sf, det_kpts,
-                     det_bboxes, N, K, rescale, sigma_ld);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<pose_finalize_kernel>(
+      dim3((unsigned)(B * N)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), kpts, sigmas, scores, wh, sf,
+      det_kpts, det_bboxes, N, K, rescale, sigma_ld);
 }
 
 // ---------------------------------------------------------------------------
@@ -542,11 +516,8 @@ extern "C" int pave_ref_update_frames_f32(const float* y, const float* ref, floa
     return pave_internal_fail(PAVE_E_ARG, "ref_update_frames: R, T, o > 0, op >= o, R %% G == 0");
   const long long n = (long long)R * T * o;
   const unsigned nb = (unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
-  hipLaunchKernelGGL(ref_update_frames_kernel, dim3(nb), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), y, ref, out, R, T, op, o, G, eps);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<ref_update_frames_kernel>(
+      dim3(nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y, ref, out, R, T, op, o, G, eps);
 }
 
 // ---------------------------------------------------------------------------
@@ -613,11 +584,9 @@ extern "C" int pave_gather_rows_add_f32(const float* src, long long src_batch_st
     return pave_internal_fail(PAVE_E_ARG, "gather_rows_add: n, Q, S > 0, C %% 4 == 0, batch stride %% 4 == 0");
   const long long total = (long long)n * Q * (C / 4);
   const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(gather_rows_add_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src,
-                     src_batch_stride, index, add, rows, sum, n, Q, S, C / 4);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<gather_rows_add_kernel>(
+      dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, src_batch_stride, index, add, rows, sum,
+      n, Q, S, C / 4);
 }
 
 extern "C" int pave_proposal_refs_f32(float* kpt, int ld, const float* props, long long props_batch_stride,
@@ -628,11 +597,9 @@ extern "C" int pave_proposal_refs_f32(float* kpt, int ld, const float* props, lo
     return pave_internal_fail(PAVE_E_ARG, "proposal_refs: n, Q, S, T > 0, K2 even, ld >= K2");
   const long long total = (long long)n * Q * K2;
   const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(proposal_refs_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), kpt, ld,
-                     props, props_batch_stride, index, refs, n, Q, S, K2, T);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<proposal_refs_kernel>(
+      dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), kpt, ld, props, props_batch_stride, index,
+      refs, n, Q, S, K2, T);
 }
 
 // pave_merge_softmax_partials_f32
@@ -681,11 +648,8 @@ extern "C" int pave_merge_softmax_partials_f32(const float* parts, float* out, i
   if (G <= 0 || U <= 0 || C <= 0 || H <= 0 || C % H != 0 || (C / H) % 4 != 0 || (2 * H) % 4 != 0)
     return pave_internal_fail(PAVE_E_ARG, "merge_softmax_partials: C / H channels per head, a multiple of 4; H even");
   const long long n = (long long)U * (C >> 2);
-  hipLaunchKernelGGL(merge_softmax_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), parts, out, G, U, C, H);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<merge_softmax_partials_kernel>(
+      dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), parts, out, G, U, C, H);
 }
 
 // pave_swin_window_attn_f32
@@ -988,15 +952,10 @@ extern "C" int pave_swin_window_attn_f32(const float* qkv, const float* bias_t, 
   if (shift < 0 || shift >= window) return pave_internal_fail(PAVE_E_ARG, "swin_window_attn: 0 <= shift < window");
   const long long nb = (long long)B * ((H + window - 1) / window) * ((W + window - 1) / window) * heads;
   if (nb >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "swin_window_attn: grid too large");
-  if (pave_internal_diag_variant() == 18)   // the per-lane form (tests compare the two)
-    hipLaunchKernelGGL((swin_window_attn_kernel<7>), dim3((unsigned)nb), dim3(64), 0,
-                       reinterpret_cast<hipStream_t>(stream), qkv, bias_t, pad_qkv, out, B, H, W, C, heads, shift,
-                       scale);
-  else
-    hipLaunchKernelGGL((swin_window_attn_mfma_kernel<7>), dim3((unsigned)nb), dim3(64), 0,
-                       reinterpret_cast<hipStream_t>(stream), qkv, bias_t, pad_qkv, out, B, H, W, C, heads, shift,
-                       scale);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (pave_internal_diag_variant() == PAVE_DV_SWIN_PER_LANE)   // the per-lane form (tests compare the two)
+    return pave_launch<swin_window_attn_kernel<7>>(dim3((unsigned)nb), dim3(64), 0, st, qkv, bias_t, pad_qkv, out, B, H,
+                                                   W, C, heads, shift, scale);
+  return pave_launch<swin_window_attn_mfma_kernel<7>>(dim3((unsigned)nb), dim3(64), 0, st, qkv, bias_t, pad_qkv, out, B,
+                                                      H, W, C, heads, shift, scale);
 }

@@ -496,17 +496,12 @@ static int enc_tile_launch(const float* value, const float* proj, const float* r
   };
   if (variant == 1) {  // +-4 px windows, 2 workgroups per CU
     fill(WinGeom<16, 12, 10, 9>{}, 16, 12, 10, 9);
-    hipLaunchKernelGGL((enc_tile_kernel<16, 12, 10, 9, 4, 4, 4, 4, 1, ABL>), dim3((unsigned)nb), dim3(384), 0, st, p);
-  } else {             // -4 .. +3 px windows (52 KB), 3 workgroups per CU
-    fill(WinGeom<14, 10, 8, 7>{}, 14, 10, 8, 7);
-    if (prepared)
-      hipLaunchKernelGGL((enc_tile_kernel<14, 10, 8, 7, 3, 3, 3, 3, 5, ABL, true>), dim3((unsigned)nb), dim3(384), 0, st, p);
-    else
-      hipLaunchKernelGGL((enc_tile_kernel<14, 10, 8, 7, 3, 3, 3, 3, 5, ABL>), dim3((unsigned)nb), dim3(384), 0, st, p);
+    return pave_launch<enc_tile_kernel<16, 12, 10, 9, 4, 4, 4, 4, 1, ABL>>(dim3((unsigned)nb), dim3(384), 0, st, p);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  fill(WinGeom<14, 10, 8, 7>{}, 14, 10, 8, 7);   // -4 .. +3 px windows (52 KB), 3 workgroups per CU
+  if (prepared)
+    return pave_launch<enc_tile_kernel<14, 10, 8, 7, 3, 3, 3, 3, 5, ABL, true>>(dim3((unsigned)nb), dim3(384), 0, st, p);
+  return pave_launch<enc_tile_kernel<14, 10, 8, 7, 3, 3, 3, 3, 5, ABL>>(dim3((unsigned)nb), dim3(384), 0, st, p);
 }
 
 extern "C" int pave_enc_deform_attn_tile_f32(const float* value, const float* proj,

@@ -1467,19 +1467,9 @@ int launch_q(const float* a, const uint16_t* w, const float* bias, const float* 
   const int smem = (QNS * STAGE > EPIB ? QNS * STAGE : EPIB) + (ABIAS ? K * 4 : 0);
   const long long gx = ((M + BM - 1) / BM) * (N / BN);
   if (gx >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_q: grid too large");
-  auto kern = gemm_q_kernel<TN, KIND, ABIAS, RM, PL, HT>;
-  static int attr_smem = 0;
-  if (smem > attr_smem) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "gemm_q: cannot raise dynamic LDS limit");
-    attr_smem = smem;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ksplit), dim3(256), smem, st, a, w, bias,
-                     residual, out, (int)M, K, N, relu, a_bias, g, os, a2);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch_lds<gemm_q_kernel<TN, KIND, ABIAS, RM, PL, HT>>(
+      "gemm_q: cannot raise dynamic LDS limit", dim3((unsigned)gx, (unsigned)ksplit), dim3(256), smem, st, a, w, bias,
+      residual, out, (int)M, K, N, relu, a_bias, g, os, a2);
 }
 
 // split-K second pass: out = act(sum over the parts IN ORDER + bias + residual), float4 per lane
@@ -1621,11 +1611,8 @@ int launch_s(const float* a, const uint16_t* w, const float* bias, const float* 
              long long M, int K, int N, int relu, int lda, int group_n, int res_rows, int n_real,
              hipStream_t st) {
   const long long tiles = ((M + 31) / 32) * ((N + 32 * TN - 1) / (32 * TN));
-  hipLaunchKernelGGL((gemm_s_kernel<TN, PF, PL>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a, w, bias,
-                     residual, out, (int)M, K, N, relu, lda, group_n, res_rows, n_real);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<gemm_s_kernel<TN, PF, PL>>(dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, a, w, bias,
+                                                residual, out, (int)M, K, N, relu, lda, group_n, res_rows, n_real);
 }
 // ---------------------------------------------------------------------------
 // Small-row form with the K axis split over the four waves of a block (round 6).  The form above gives a wave
@@ -1741,11 +1728,8 @@ int launch_sk(const float* a, const uint16_t* w, const float* bias, const float*
               long long M, int K, int N, int relu, int lda, int group_n, int res_rows, int n_real,
               hipStream_t st) {
   const long long tiles = ((M + 31) / 32) * ((N + 31) / 32);
-  hipLaunchKernelGGL((gemm_sk_kernel<4, PL>), dim3((unsigned)tiles), dim3(256), 0, st, a, w, bias, residual, out,
-                     (int)M, K, N, relu, lda, group_n, res_rows, n_real);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<gemm_sk_kernel<4, PL>>(dim3((unsigned)tiles), dim3(256), 0, st, a, w, bias, residual, out,
+                                            (int)M, K, N, relu, lda, group_n, res_rows, n_real);
 }
 // ---------------------------------------------------------------------------
 // The K-split form with TN 32-column tiles per block (form policy 2 above kSkRows rows: the decoders' Linears of
@@ -1865,11 +1849,9 @@ int launch_skm(const float* a, const uint16_t* w, const float* bias, const float
                hipStream_t st) {
   const long long blocks = ((M + 31) / 32) * ((N + 32 * kSkmTiles - 1) / (32 * kSkmTiles));
   if (blocks >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_skm: grid too large");
-  hipLaunchKernelGGL((gemm_skm_kernel<kSkmTiles, 2, PL>), dim3((unsigned)blocks), dim3(256), 0, st, a, w, bias,
-                     residual, out, (int)M, K, N, relu, lda, group_n, res_rows, n_real);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<gemm_skm_kernel<kSkmTiles, 2, PL>>(dim3((unsigned)blocks), dim3(256), 0, st, a, w, bias,
+                                                        residual, out, (int)M, K, N, relu, lda, group_n, res_rows,
+                                                        n_real);
 }
 // Taken from K = 512 on, up to kSkTiles blocks (tools/small_gemm_ksplit_ab.py, us per launch behind a busy stream,
 // K-split | one-wave form | tile kernels): at K = 256 a wave's whole walk is 16 slabs and the split only adds blocks
@@ -1925,11 +1907,13 @@ inline bool rows_ksplit(long long M, int N, int K, int policy) {
 // policies 1 and 2 take it at every M (in row chunks below its 4 GiB identity-buffer limit).
 inline void ln_form(long long M, int K, int N, int policy, int dv, bool* lnpass, bool* ksplit, bool* wide) {
   if (policy == 0) {
-    *lnpass = small_rows_form(M, N) && (dv == 0 || dv == 19);
-    *ksplit = *lnpass && small_rows_ksplit_form(M, N, K) && dv == 0;
-    *wide = dv != 13 && ((M + QBM - 1) / QBM >= 512 || dv == 14) && M * 1024ll < (1ll << 32);
+    *lnpass = small_rows_form(M, N) && (dv == PAVE_DV_NONE || dv == PAVE_DV_SMALL_ROWS_R5);
+    *ksplit = *lnpass && small_rows_ksplit_form(M, N, K) && dv == PAVE_DV_NONE;
+    *wide = dv != PAVE_DV_LN_8WAVE && ((M + QBM - 1) / QBM >= 512 || dv == PAVE_DV_LN_WIDE) &&
+            M * 1024ll < (1ll << 32);
   } else {
-    *lnpass = *ksplit = policy == 2 && ksplit_order_applies(K, N) && (dv == 0 || dv == 21);
+    *lnpass = *ksplit =
+        policy == 2 && ksplit_order_applies(K, N) && (dv == PAVE_DV_NONE || dv == PAVE_DV_SK_ANY_ROWS);
     *wide = true;
   }
 }
@@ -1949,27 +1933,27 @@ int launch_w(const float* a, const uint16_t* w, const float* bias, const float* 
              const float* a2 = nullptr, int ksplit = 1) {
   const long long gx = ((M + QBM - 1) / QBM) * (N / 256);
   if (gx >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_w: grid too large");
-  auto kern = gemm_w_kernel<KIND, PL>;
-  // (diag variant 20, tools/coresidency_probe.py: 40 KiB more dynamic LDS than the kernel uses, so that ONE block
-  // fits a CU instead of two -- what a GEMM that leaves room for a co-resident sampler block would look like)
+  // (PAVE_DV_WIDE_ONE_PER_CU, tools/coresidency_probe.py: 40 KiB more dynamic LDS than the kernel uses, so that ONE
+  // block fits a CU instead of two -- what a GEMM that leaves room for a co-resident sampler block would look like)
 #ifdef PAVE_DIAG
   constexpr int kPad = 40 * 1024;
 #else
   constexpr int kPad = 0;
 #endif
-  const int smem = w_smem<PL>() + (pave_internal_diag_variant() == 20 ? kPad : 0);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, w_smem<PL>() + kPad) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "gemm_w: cannot raise dynamic LDS limit");
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ksplit), dim3(256), smem, st, a, w, bias,
-                     residual, out, (int)M, K, N, relu, g, os, a2);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  const int smem = w_smem<PL>() + (pave_internal_diag_variant() == PAVE_DV_WIDE_ONE_PER_CU ? kPad : 0);
+  return pave_launch_lds<gemm_w_kernel<KIND, PL>>("gemm_w: cannot raise dynamic LDS limit",
+                                                  dim3((unsigned)gx, (unsigned)ksplit), dim3(256), smem, st, a, w,
+                                                  bias, residual, out, (int)M, K, N, relu, g, os, a2);
+}
+
+// the mixed-tile form: wide tiles + one 128-column narrow tail
+template <int PL>
+int launch_wn(const float* a, const uint16_t* w, const float* bias, const float* residual, float* out, long long M,
+              int K, int N, int relu, hipStream_t st, const QConv g, const QOut os) {
+  const long long gx = ((M + QBM - 1) / QBM) * (N / 256 + 1);
+  if (gx >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_wn: grid too large");
+  return pave_launch_lds<gemm_wn_kernel<PL>>("gemm_wn: cannot raise dynamic LDS limit", dim3((unsigned)gx), dim3(256),
+                                             wn_smem<PL>(), st, a, w, bias, residual, out, (int)M, K, N, relu, g, os);
 }
 
 }  // namespace
@@ -1993,7 +1977,7 @@ static void splitk_plan(long long M, int Kp, int Np, int policy, int* ksplit, in
   // the last bits between classes (a one-clip batch against the 28-frame bench batch) -- as they do between the
   // row-GEMM forms that are chosen by tile count (small-row form, wide form, 256-row chain tiles).  The parity
   // tests compare compositions at 1e-4 relative; nothing in the package relies on cross-composition bit equality.
-  if (tiles >= 200 || nsl < 128 || pave_internal_diag_variant() == 6) return;
+  if (tiles >= 200 || nsl < 128 || pave_internal_diag_variant() == PAVE_DV_NO_SPLITK) return;
   // 2 048 <= K < 8 192 (the ChannelMapper's extra level behind HRNet-w48: 3x3 / stride 2 on 384 channels,
   // K = 3 456; ResNet layer3 / layer4's 3x3 on a one-clip batch): 4 parts
   // below 128 tiles (tools/conv_small_batch.py: 256 -> 256 on 3 x 50 x 84, 99 tiles, 113 -> 101 us;
@@ -2035,14 +2019,15 @@ extern "C" int pave_form_plan(long long M, int K, int N, int kind, int nplanes, 
   int parts = 1, per = 0;
   switch (kind) {
     case PAVE_FORM_ROWS_SPLITK:   // pave_gemm_bf16x3_splitk_f32 where pave_gemm_splitk_workspace_bytes > 0
-      if (dv != 9) splitk_plan(M, Kp, Np, policy, &parts, &per);
+      if (dv != PAVE_DV_FIRST_GEN) splitk_plan(M, Kp, Np, policy, &parts, &per);
       if (parts > 1) {
         *order = PAVE_ORDER_SPLITK, *ksplit = parts;
         break;
       }
       [[fallthrough]];
     case PAVE_FORM_ROWS:
-      if (rows_ksplit(M, Np, Kp, policy) && (dv == 0 || dv == 21)) *order = PAVE_ORDER_KSPLIT;
+      if (rows_ksplit(M, Np, Kp, policy) && (dv == PAVE_DV_NONE || dv == PAVE_DV_SK_ANY_ROWS))
+        *order = PAVE_ORDER_KSPLIT;
       break;
     case PAVE_FORM_LN: {
       bool lnpass, sk, wide;
@@ -2052,7 +2037,7 @@ extern "C" int pave_form_plan(long long M, int K, int N, int kind, int nplanes, 
       break;
     }
     case PAVE_FORM_CONV3X3:
-      if (dv != 9) splitk_plan(M, Kp, Np, policy, &parts, &per);
+      if (dv != PAVE_DV_FIRST_GEN) splitk_plan(M, Kp, Np, policy, &parts, &per);
       if (parts > 1) *order = PAVE_ORDER_SPLITK, *ksplit = parts;
       break;
     default:   // PAVE_FORM_ROWS_TILE, PAVE_FORM_CONV1X1S, PAVE_FORM_ENCPROJ: the tile kernels at every M
@@ -2063,28 +2048,29 @@ extern "C" int pave_form_plan(long long M, int K, int N, int kind, int nplanes, 
 int pave_internal_splitk_reduce(const float* ws, int parts, long long M, int n, const float* bias,
                                 const float* residual, int relu, float* out, void* stream) {
   const long long total4 = M * n / 4;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), ws, parts, total4, n / 4, bias, residual, relu,
-                     out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<splitk_reduce_kernel>(dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0,
+                                           reinterpret_cast<hipStream_t>(stream), ws, parts, total4, n / 4, bias,
+                                           residual, relu, out);
 }
 
-// Internal entries (pave_gemm_split.hip dispatches here).  kind as the kernel's KIND; the geometry
-// is ignored for kind 0.
+// Internal entries (pave_gemm_split.hip dispatches here).
 template <int PL>
-static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_planes, const float* bias,
-                           const float* residual, long long residual_rows, float* out, float* out2,
-                           int n_split, long long M, int K, int N, int relu, int kind, int H, int W,
-                           int Cin, int Ho, int Wo, int stride, void* stream, const float* a2, int n_real,
-                           int ksplit, int ks_slabs) {
+static int gemm_q_dispatch(const GemmQ& q) {
+  const float *a = q.a, *a_bias = q.a_bias, *bias = q.bias, *residual = q.residual, *a2 = q.a2;
+  float *out = q.out, *out2 = q.out2;
+  const long long M = q.M;
+  const int K = q.K, N = q.N, relu = q.relu, n_split = q.n_split, ks_slabs = q.ks_slabs;
+  const int kind = q.rows, Ho = q.Ho, Wo = q.Wo, stride = q.stride;
+  // the kernels' QConv carries the row forms' values in the geometry's slots: the row stride and the column
+  // group in H and W (GEMMQ_ROWS; the geometry is ignored there), K1 in Cin (GEMMQ_ROWS2)
+  const int H = kind == GEMMQ_ROWS ? q.lda : q.H, W = kind == GEMMQ_ROWS ? q.group_n : q.W;
+  const int Cin = kind == GEMMQ_ROWS2 ? q.k1 : q.Cin;
+  int n_real = q.n_real, ksplit = q.ksplit;
   const QConv g{H, W, Cin, Ho, Wo, stride,
                 (kind == 1 && Cin > 16) ? (unsigned)(((1ull << 32) + (Cin >> 4) - 1) / (unsigned)(Cin >> 4)) : 0u};
   if (relu < 0 || relu > 3)
     return pave_internal_fail(PAVE_E_ARG, "gemm_q: activation 0 (none), 1 (ReLU), 2 (GELU) or 3 (sigmoid)");
-  const bool narrow = N < 0;   // (grouped rows with 64-column groups: 64-wide tiles)
-  if (narrow) N = -N;
+  const bool narrow = q.narrow_groups;   // (grouped rows with 64-column groups: 64-wide tiles)
   if (n_real <= 0) n_real = N;
   if (n_real > N || n_real % 4 != 0 || (out2 && n_real != N))
     return pave_internal_fail(PAVE_E_ARG, "gemm_q: n_real %% 4 == 0, n_real <= N (== N with two outputs)");
@@ -2092,10 +2078,10 @@ static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_pl
                      (long long)(ksplit - 1) * ks_slabs + 4 > K / 16 || (long long)ksplit * ks_slabs < K / 16))
     return pave_internal_fail(PAVE_E_ARG, "gemm_q: split-K parts are raw partial sums of >= 4 slabs");
   if (ksplit < 1) ksplit = 1;
-  const QOut os{out2, out2 ? n_split : 0, residual_rows >= M ? 0 : (int)residual_rows, n_real,
+  const QOut os{out2, out2 ? n_split : 0, q.residual_rows >= M ? 0 : (int)q.residual_rows, n_real,
                 ksplit > 1 ? ks_slabs : 0};
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const uint16_t* w = static_cast<const uint16_t*>(w_planes);
+  hipStream_t st = reinterpret_cast<hipStream_t>(q.stream);
+  const uint16_t* w = static_cast<const uint16_t*>(q.w_planes);
   if (K % 32 != 0 || K < 64) return pave_internal_fail(PAVE_E_ARG, "gemm_q: K %% 32 == 0, K >= 64");
   // the epilogue reads a row-periodic table / writes a tile's rows through 32-bit buffer offsets
   if ((os.res_rows != 0 && (long long)os.res_rows * n_real * 4 >= (1ll << 31)) || (long long)N * 512 >= (1ll << 31))
@@ -2117,27 +2103,27 @@ static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_pl
   // 38 -> 76 us), so they keep those.  Measured with it: 1200 x 1024 x 256 + LayerNorm 62 -> 35 us,
   // 1200 x 256 x 256 + LayerNorm 24 -> 19 us.
   // ... and, from round 6 on, with the K axis split over the block's four waves wherever the launch is at most
-  // kSkTiles 32 x 32 tiles, at ANY output width (diag variant 19: the forms as they were, for A/B and the tests
-  // that compare the one-wave form with the tile kernels bit for bit)
+  // kSkTiles 32 x 32 tiles, at ANY output width (PAVE_DV_SMALL_ROWS_R5: the forms as they were, for A/B and the
+  // tests that compare the one-wave form with the tile kernels bit for bit)
   // (form policy 1: never; 2: wherever ksplit_order_applies(K, N), above kSkRows rows with kSkmTiles column tiles
-  // per block -- the same order; diag variant 21: gemm_sk_kernel there too)
-  const int dv0 = pave_internal_diag_variant();
+  // per block -- the same order; PAVE_DV_SK_ANY_ROWS: gemm_sk_kernel there too)
+  const int dv = pave_internal_diag_variant();
   if (kind == 0 && rows_ksplit(M, N, K, pave_internal_form_policy()) && !a_bias && !out2 && ksplit == 1 &&
-      (dv0 == 0 || dv0 == 21)) {
-    if (M > kSkRows && dv0 != 21 && (W <= 0 || W % (32 * kSkmTiles) == 0))
+      (dv == PAVE_DV_NONE || dv == PAVE_DV_SK_ANY_ROWS)) {
+    if (M > kSkRows && dv != PAVE_DV_SK_ANY_ROWS && (W <= 0 || W % (32 * kSkmTiles) == 0))
       return launch_skm<PL>(a, w, bias, residual, out, M, K, N, relu, H > 0 ? H : K, W > 0 ? W : 0, os.res_rows,
                             n_real, st);
     return launch_sk<PL>(a, w, bias, residual, out, M, K, N, relu, H > 0 ? H : K, W > 0 ? W : 0, os.res_rows,
                          n_real, st);
   }
   if (kind == 0 && small_rows_form(M, N) && N <= 512 && !a_bias && !out2 && ksplit == 1 &&
-      (pave_internal_diag_variant() == 0 || pave_internal_diag_variant() == 19))
+      (dv == PAVE_DV_NONE || dv == PAVE_DV_SMALL_ROWS_R5))
     return launch_s<1, 4, PL>(a, w, bias, residual, out, M, K, N, relu, H > 0 ? H : K, W > 0 ? W : 0, os.res_rows,
                           n_real, st);
   // 3x3 form: buffer-addressed below 4 GiB of map (a lane's byte offset is 32 bits wide)
-  // (diag variant 5: the 64-bit lane-address form everywhere, for A/B)
+  // (PAVE_DV_CONV3_ADDR64: the 64-bit lane-address form everywhere, for A/B)
   const bool big3 = kind == 1 && ((M / ((long long)Ho * Wo)) * H * W * Cin * 4 >= (1ll << 32) - 65536 ||
-                                  pave_internal_diag_variant() == 5);
+                                  dv == PAVE_DV_CONV3_ADDR64);
 #define PAVE_QGO(TN_)                                                                               \
   if (kind == 0) {                                                                                  \
     if (a_bias) return launch_q<TN_, 0, true, 1, PL>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os); \
@@ -2150,9 +2136,9 @@ static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_pl
   // the wide form (32 x 256 per wave): whole 256-column tiles, about one tile per block slot
   // of the chip (2 blocks x 256 CUs) -- below that the narrow form's twice as many tiles fill
   // the CUs better
-  const int dv = pave_internal_diag_variant();
   const long long wtiles = ((M + QBM - 1) / QBM) * (N / 256) * ksplit;
-  if (N % 256 == 0 && n_real == N && !narrow && !a_bias && dv != 8 && (wtiles >= 400 || dv == 7) &&
+  if (N % 256 == 0 && n_real == N && !narrow && !a_bias && dv != PAVE_DV_WIDE_NEVER &&
+      (wtiles >= 400 || dv == PAVE_DV_WIDE_ALWAYS) &&
       !(kind == 0 && W > 0 && W % 256 != 0) && (!out2 || n_split % 256 == 0)) {
     if (kind == 0) return launch_w<0, PL>(a, w, bias, residual, out, M, K, N, relu, st, g, os, nullptr, ksplit);
     if (kind == 1 && big3) return launch_w<2, PL>(a, w, bias, residual, out, M, K, N, relu, st, g, os, nullptr, ksplit);
@@ -2160,39 +2146,27 @@ static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_pl
     if (kind == 4) return launch_w<4, PL>(a, w, bias, residual, out, M, K, N, relu, st, g, os, a2, ksplit);
     return launch_w<3, PL>(a, w, bias, residual, out, M, K, N, relu, st, g, os, nullptr, ksplit);
   }
-  if (kind == 0 && N % 256 == 128 && N >= 384 && n_real == N && !narrow && !a_bias && dv != 8 && W == 0 && ksplit == 1 &&
-      (((M + QBM - 1) / QBM) * (N / 256 + 1) >= 400 || dv == 7) && (!out2 || n_split % 256 == 0)) {
-    const long long gx = ((M + QBM - 1) / QBM) * (N / 256 + 1);
-    if (gx >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_wn: grid too large");
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_wn_kernel<PL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, wn_smem<PL>()) != hipSuccess)
-        return pave_internal_fail(PAVE_E_LAUNCH, "gemm_wn: cannot raise dynamic LDS limit");
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(gemm_wn_kernel<PL>, dim3((unsigned)gx), dim3(256), wn_smem<PL>(), st, a, w, bias, residual, out,
-                       (int)M, K, N, relu, g, os);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-    return PAVE_OK;
-  }
+  if (kind == 0 && N % 256 == 128 && N >= 384 && n_real == N && !narrow && !a_bias && dv != PAVE_DV_WIDE_NEVER &&
+      W == 0 && ksplit == 1 && (((M + QBM - 1) / QBM) * (N / 256 + 1) >= 400 || dv == PAVE_DV_WIDE_ALWAYS) &&
+      (!out2 || n_split % 256 == 0))
+    return launch_wn<PL>(a, w, bias, residual, out, M, K, N, relu, st, g, os);
   // 65..96 real outputs in 128-row planes (HRNet's 96-channel branch): three column tiles instead of four
-  if (N == 128 && n_real <= 96 && n_real > 64 && !narrow && !out2 && pave_internal_diag_variant() != 8 &&
+  if (N == 128 && n_real <= 96 && n_real > 64 && !narrow && !out2 && dv != PAVE_DV_WIDE_NEVER &&
       ksplit == 1 && (kind == 1 || kind == 0) && !a_bias) {
     if (kind == 1 && big3) return launch_q<3, 2, false, 1, PL>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os);
-    if (kind == 1 && dv != 15 && (((M + 255) / 256) >= 1024 || dv == 16) && (os.res_rows == 0 || os.res_rows >= 64))
+    if (kind == 1 && dv != PAVE_DV_RM2_NEVER && (((M + 255) / 256) >= 1024 || dv == PAVE_DV_RM2_ALWAYS) &&
+        (os.res_rows == 0 || os.res_rows >= 64))
       return launch_q<3, 1, false, 2, PL>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os);
     if (kind == 1) return launch_q<3, 1, false, 1, PL>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os);
     return launch_q<3, 0, false, 1, PL>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os);
   }
   if (N % 128 == 0 && !narrow) { PAVE_QGO(4); }
-  // 64-column tiles with two row tiles per wave (256-row blocks): only on request (diag variant 16).  Measured
+  // 64-column tiles with two row tiles per wave (256-row blocks): only on request (PAVE_DV_RM2_ALWAYS).  Measured
   // at 28 x 200 x 336 pixels (tools/rm_ab.py, profiles/r05_rm_ab.txt): 3x3 48 -> 48 + identity 628 -> 653 us,
   // 64 -> 64 801 -> 817, conv1 256 -> 64 470 -> 478 -- as launches of their own these forms lose more from two
   // blocks per CU (196 registers) instead of three than they gain from sharing the W fragments; the 96-column
   // 3x3 (two blocks per CU either way: 442 -> 428 us) and the layer1 chain (-3 ... -4 %) take the form.
-  if (N % 64 == 0 && (kind == 0 || (kind == 1 && !big3)) && !a_bias && ksplit == 1 && dv == 16 &&
+  if (N % 64 == 0 && (kind == 0 || (kind == 1 && !big3)) && !a_bias && ksplit == 1 && dv == PAVE_DV_RM2_ALWAYS &&
       (os.res_rows == 0 || os.res_rows >= 64) && (long long)N * 1024 < (1ll << 31)) {
     if (kind == 1) return launch_q<2, 1, false, 2, PL>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os);
     return launch_q<2, 0, false, 2, PL>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os);
@@ -2200,10 +2174,11 @@ static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_pl
   // 33 .. 48 real outputs in 64-row planes (HRNet-w48's 48-channel 3x3 branch, 154 launches of a T = 7 x 4 step):
   // the 16-column tail on v_mfma_f32_16x16x32_bf16 over slab pairs instead of zero-padded 32x32x16 products
   // (HT above).  The 3x3 form only: it takes the tile kernels at every size, so a clip's values do not depend on
-  // the batch it is in.  (diag variant 17: never -- the padded form, for A/B and the tolerance test)
+  // the batch it is in.  (PAVE_DV_NO_HALF_TAIL: never -- the padded form, for A/B and the tolerance test)
   if constexpr (PL == 3) {
     if (N == 64 && n_real > 32 && n_real <= 48 && kind == 1 && !big3 && !a_bias && !out2 && ksplit == 1 &&
-        dv != 17 && dv != 15 && dv != 16)   // (15 / 16: the A/B of the padded one- / two-row-tile forms)
+        dv != PAVE_DV_NO_HALF_TAIL && dv != PAVE_DV_RM2_NEVER &&
+        dv != PAVE_DV_RM2_ALWAYS)   // (RM2_*: the A/B of the padded one- / two-row-tile forms)
       return launch_q<2, 1, false, 1, 3, true>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g, os);
   }
   if (N % 64 == 0) { PAVE_QGO(2); }
@@ -2211,18 +2186,9 @@ static int gemm_q_dispatch(const float* a, const float* a_bias, const void* w_pl
   return pave_internal_fail(PAVE_E_ARG, "gemm_q: N %% 64 == 0 required");
 }
 
-int pave_internal_gemm_q(const float* a, const float* a_bias, const void* w_planes, const float* bias,
-                         const float* residual, long long residual_rows, float* out, float* out2,
-                         int n_split, long long M, int K, int N, int relu, int kind, int H, int W,
-                         int Cin, int Ho, int Wo, int stride, void* stream, const float* a2, int n_real,
-                         int ksplit, int ks_slabs, int planes) {
-  // planes: 3 = the exact bf16 split, 1 = one plane of fp16 operands (PAVE_PLANES_FP16 at the C ABI)
-  if (planes == 1)
-    return gemm_q_dispatch<1>(a, a_bias, w_planes, bias, residual, residual_rows, out, out2, n_split, M, K, N, relu,
-                              kind, H, W, Cin, Ho, Wo, stride, stream, a2, n_real, ksplit, ks_slabs);
-  if (planes != 3) return pave_internal_fail(PAVE_E_ARG, "gemm_q: 3 bf16 planes or 1 fp16 plane");
-  return gemm_q_dispatch<3>(a, a_bias, w_planes, bias, residual, residual_rows, out, out2, n_split, M, K, N, relu,
-                            kind, H, W, Cin, Ho, Wo, stride, stream, a2, n_real, ksplit, ks_slabs);
+int pave_internal_gemm_q(const GemmQ& q) {
+  return pave_with_planes(q.planes, "gemm_q: 3 bf16 planes or 1 fp16 plane",
+                          [&](auto pl) { return gemm_q_dispatch<decltype(pl)::value>(q); });
 }
 
 // merged encoder projection with the sampler's softmax / location arithmetic in the epilogue
@@ -2244,27 +2210,18 @@ static int gemm_encproj_go(const float* a, const void* w_planes, const float* ta
   const QOut os{samp, 256, table_rows >= M ? 0 : (int)table_rows, 640, 0};
   const long long gx = ((M + QBM - 1) / QBM) * 3;
   if (gx >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_encproj: grid too large");
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_wn_enc_kernel<PL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, wn_smem<PL>()) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "gemm_encproj: cannot raise dynamic LDS limit");
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gemm_wn_enc_kernel<PL>, dim3((unsigned)gx), dim3(256), wn_smem<PL>(),
-                     reinterpret_cast<hipStream_t>(stream), a, static_cast<const uint16_t*>(w_planes), table,
-                     value_bias, value, (int)M, K, os, epi);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch_lds<gemm_wn_enc_kernel<PL>>(
+      "gemm_encproj: cannot raise dynamic LDS limit", dim3((unsigned)gx), dim3(256), wn_smem<PL>(),
+      reinterpret_cast<hipStream_t>(stream), a, static_cast<const uint16_t*>(w_planes), table, value_bias, value,
+      (int)M, K, os, epi);
 }
 int pave_internal_gemm_encproj(const float* a, const void* w_planes, const float* table, long long table_rows,
                                const float* value_bias, const float* ref, const int* levels_hw, float* value,
                                float* samp, long long M, int K, void* stream, int planes) {
-  if (planes == 1)
-    return gemm_encproj_go<1>(a, w_planes, table, table_rows, value_bias, ref, levels_hw, value, samp, M, K, stream);
-  if (planes != 3) return pave_internal_fail(PAVE_E_ARG, "gemm_encproj: 3 bf16 planes or 1 fp16 plane");
-  return gemm_encproj_go<3>(a, w_planes, table, table_rows, value_bias, ref, levels_hw, value, samp, M, K, stream);
+  return pave_with_planes(planes, "gemm_encproj: 3 bf16 planes or 1 fp16 plane", [&](auto pl) {
+    return gemm_encproj_go<decltype(pl)::value>(a, w_planes, table, table_rows, value_bias, ref, levels_hw, value,
+                                                samp, M, K, stream);
+  });
 }
 
 template <int PL>
@@ -2275,72 +2232,51 @@ static int gemm_q_ln_go(const float* a, const void* w_planes, const float* bias,
     return pave_internal_fail(PAVE_E_UNSUPPORTED, "gemm_q_ln: K %% 32 == 0, K >= 64 and N == 256 required");
   bool lnpass, sk, wide;
   ln_form(M, K, N, pave_internal_form_policy(), pave_internal_diag_variant(), &lnpass, &sk, &wide);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const uint16_t* w = static_cast<const uint16_t*>(w_planes);
   if (lnpass) {
     // few rows: the small-row GEMM (bias + identity in its epilogue), then LayerNorm in place -- two
     // launches of a few microseconds instead of 10 row tiles walking K behind barriers
     // (form policy 2: at every M, the multi-tile K-split form above kSkRows rows)
-    const int st1 = sk
-        ? ((M > kSkRows && pave_internal_diag_variant() != 21)
-               ? launch_skm<PL>(a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, K, 0, 0,
-                                N, reinterpret_cast<hipStream_t>(stream))
-               : launch_sk<PL>(a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, K, 0, 0,
-                               N, reinterpret_cast<hipStream_t>(stream)))
-        : launch_s<1, 4, PL>(a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, K,
-                                   0, 0, N, reinterpret_cast<hipStream_t>(stream));
+    const int st1 = sk ? ((M > kSkRows && pave_internal_diag_variant() != PAVE_DV_SK_ANY_ROWS)
+                              ? launch_skm<PL>(a, w, bias, residual, out, M, K, N, 0, K, 0, 0, N, st)
+                              : launch_sk<PL>(a, w, bias, residual, out, M, K, N, 0, K, 0, 0, N, st))
+                       : launch_s<1, 4, PL>(a, w, bias, residual, out, M, K, N, 0, K, 0, 0, N, st);
     if (st1 != PAVE_OK) return st1;
     return pave_bias_add_layernorm_f32(out, nullptr, nullptr, gamma, beta, out, M, N, eps, stream);
   }
-  constexpr int STAGE = QBM * 64 + PL * 256 * 32;
-  constexpr int smem = QNS * STAGE + 2 * QBM * 2 * 4;
-  auto kern = gemm_q_ln_kernel<PL>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "gemm_q_ln: cannot raise dynamic LDS limit");
-    attr_set = true;
-  }
-  const long long gx = (M + QBM - 1) / QBM;
   // From two tiles per CU slot on: the wide form (4 waves, a wave owns 32 whole rows; LayerNorm on the
   // accumulator layout, two blocks per CU) -- 602 -> 548 us at K = 256, 1 715 -> 1 606 us at K = 1024 for
   // 625 044 rows (tools/ln_ab.py).  Few tiles (the decoders' M = 1 200) keep the 8-wave block: twice the
-  // waves per tile.  (diag variant 13: always the 8-wave form, 14: always the wide form; form policies 1 / 2:
-  // always the wide form -- ln_form.)  The identity rows are read through a buffer resource: M * 1024 bytes
-  // < 4 GiB, so beyond 2^22 rows (policies 1 / 2 only) the launch goes in row chunks of whole 128-row tiles --
-  // a row's values do not depend on the tile it sits in.
-  if (wide) {
-    static bool attr_w = false;
-    if (!attr_w) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_w_ln_kernel<PL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, w_smem<PL>()) != hipSuccess)
-        return pave_internal_fail(PAVE_E_LAUNCH, "gemm_w_ln: cannot raise dynamic LDS limit");
-      attr_w = true;
-    }
-    constexpr long long kChunk = (1ll << 22) - QBM;
-    for (long long r0 = 0; r0 < M; r0 += kChunk) {
-      const long long m = M - r0 < kChunk ? M - r0 : kChunk;
-      hipLaunchKernelGGL(gemm_w_ln_kernel<PL>, dim3((unsigned)((m + QBM - 1) / QBM)), dim3(256), w_smem<PL>(),
-                         reinterpret_cast<hipStream_t>(stream), a + r0 * K, static_cast<const uint16_t*>(w_planes),
-                         bias, residual ? residual + r0 * N : nullptr, out + r0 * N, (int)m, K, N,
-                         QLn{gamma, beta, eps});
-      const hipError_t ew = hipGetLastError();
-      if (ew != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(ew));
-    }
-    return PAVE_OK;
+  // waves per tile.  (PAVE_DV_LN_8WAVE: always the 8-wave form, PAVE_DV_LN_WIDE: always the wide form; form
+  // policies 1 / 2: always the wide form -- ln_form.)
+  if (!wide) {
+    constexpr int STAGE = QBM * 64 + PL * 256 * 32;
+    constexpr int smem = QNS * STAGE + 2 * QBM * 2 * 4;
+    return pave_launch_lds<gemm_q_ln_kernel<PL>>("gemm_q_ln: cannot raise dynamic LDS limit",
+                                                 dim3((unsigned)((M + QBM - 1) / QBM)), dim3(512), smem, st, a, w,
+                                                 bias, residual, out, (int)M, K, N, QLn{gamma, beta, eps});
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), smem,
-                     reinterpret_cast<hipStream_t>(stream), a, static_cast<const uint16_t*>(w_planes),
-                     bias, residual, out, (int)M, K, N, QLn{gamma, beta, eps});
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
+  // The identity rows are read through a buffer resource: M * 1024 bytes < 4 GiB, so beyond 2^22 rows (policies
+  // 1 / 2 only) the launch goes in row chunks of whole 128-row tiles -- a row's values do not depend on the tile
+  // it sits in.
+  constexpr long long kChunk = (1ll << 22) - QBM;
+  for (long long r0 = 0; r0 < M; r0 += kChunk) {
+    const long long m = M - r0 < kChunk ? M - r0 : kChunk;
+    const int rc = pave_launch_lds<gemm_w_ln_kernel<PL>>(
+        "gemm_w_ln: cannot raise dynamic LDS limit", dim3((unsigned)((m + QBM - 1) / QBM)), dim3(256), w_smem<PL>(),
+        st, a + r0 * K, w, bias, residual ? residual + r0 * N : nullptr, out + r0 * N, (int)m, K, N,
+        QLn{gamma, beta, eps});
+    if (rc != PAVE_OK) return rc;
+  }
   return PAVE_OK;
 }
 int pave_internal_gemm_q_ln(const float* a, const void* w_planes, const float* bias, const float* residual,
                             const float* gamma, const float* beta, float eps, float* out, long long M,
                             int K, int N, void* stream, int planes) {
-  if (planes == 1) return gemm_q_ln_go<1>(a, w_planes, bias, residual, gamma, beta, eps, out, M, K, N, stream);
-  if (planes != 3) return pave_internal_fail(PAVE_E_ARG, "gemm_q_ln: 3 bf16 planes or 1 fp16 plane");
-  return gemm_q_ln_go<3>(a, w_planes, bias, residual, gamma, beta, eps, out, M, K, N, stream);
+  return pave_with_planes(planes, "gemm_q_ln: 3 bf16 planes or 1 fp16 plane", [&](auto pl) {
+    return gemm_q_ln_go<decltype(pl)::value>(a, w_planes, bias, residual, gamma, beta, eps, out, M, K, N, stream);
+  });
 }
 
 // fp16 mode with fp16 ACTIVATIONS around a launch (wide tile forms only): a_f16 -- the A rows are fp16 [M, K];
@@ -2360,55 +2296,44 @@ int pave_internal_gemm_f16act(const void* a, int a_f16, const void* w_plane, con
   const uint16_t* w = static_cast<const uint16_t*>(w_plane);
   const float* af = static_cast<const float*>(a);
   float* of = static_cast<float*>(out);
-  const QConv g0{0, 0, 0, 0, 0, 0, 0u};
   const long long gx = ((M + QBM - 1) / QBM) * (N / 256);
   if (gx >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_fp16_act: grid too large");
-#define PAVE_F16_GO(KERN, ...)                                                                        \
-  {                                                                                                   \
-    static bool attr = false;                                                                         \
-    if (!attr) {                                                                                      \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              w_smem<1>()) != hipSuccess)                                             \
-        return pave_internal_fail(PAVE_E_LAUNCH, "gemm_fp16_act: cannot raise dynamic LDS limit");    \
-      attr = true;                                                                                    \
-    }                                                                                                 \
-    hipLaunchKernelGGL(KERN, dim3((unsigned)gx), dim3(256), w_smem<1>(), st, __VA_ARGS__);            \
-  }
+  const dim3 grid((unsigned)gx), block(256);
+  constexpr const char* what = "gemm_fp16_act: cannot raise dynamic LDS limit";
   if (gamma) {
     const QLn ln{gamma, beta, eps};
-    if (a_f16) PAVE_F16_GO((gemm_w_ln_kernel<1, 1>), af, w, bias, residual, of, (int)M, K, N, ln)
-    else PAVE_F16_GO((gemm_w_ln_kernel<1, 0>), af, w, bias, residual, of, (int)M, K, N, ln)
-  } else {
-    const QOut os{nullptr, 0, 0, N, 0};
-    const int io = (a_f16 ? 1 : 0) | (out_f16 ? 2 : 0);
-    if (io == 0) PAVE_F16_GO((gemm_w_kernel<0, 1, 0>), af, w, bias, nullptr, of, (int)M, K, N, relu, g0, os, nullptr)
-    else if (io == 1) PAVE_F16_GO((gemm_w_kernel<0, 1, 1>), af, w, bias, nullptr, of, (int)M, K, N, relu, g0, os, nullptr)
-    else if (io == 2) PAVE_F16_GO((gemm_w_kernel<0, 1, 2>), af, w, bias, nullptr, of, (int)M, K, N, relu, g0, os, nullptr)
-    else PAVE_F16_GO((gemm_w_kernel<0, 1, 3>), af, w, bias, nullptr, of, (int)M, K, N, relu, g0, os, nullptr)
+    if (a_f16)
+      return pave_launch_lds<gemm_w_ln_kernel<1, 1>>(what, grid, block, w_smem<1>(), st, af, w, bias, residual, of,
+                                                     (int)M, K, N, ln);
+    return pave_launch_lds<gemm_w_ln_kernel<1, 0>>(what, grid, block, w_smem<1>(), st, af, w, bias, residual, of,
+                                                   (int)M, K, N, ln);
   }
-#undef PAVE_F16_GO
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  const QConv g0{};
+  const QOut os{nullptr, 0, 0, N, 0};
+  const float* const none = nullptr;
+  switch ((a_f16 ? 1 : 0) | (out_f16 ? 2 : 0)) {
+    case 0:
+      return pave_launch_lds<gemm_w_kernel<0, 1, 0>>(what, grid, block, w_smem<1>(), st, af, w, bias, none, of, (int)M,
+                                                     K, N, relu, g0, os, none);
+    case 1:
+      return pave_launch_lds<gemm_w_kernel<0, 1, 1>>(what, grid, block, w_smem<1>(), st, af, w, bias, none, of, (int)M,
+                                                     K, N, relu, g0, os, none);
+    case 2:
+      return pave_launch_lds<gemm_w_kernel<0, 1, 2>>(what, grid, block, w_smem<1>(), st, af, w, bias, none, of, (int)M,
+                                                     K, N, relu, g0, os, none);
+    default:
+      return pave_launch_lds<gemm_w_kernel<0, 1, 3>>(what, grid, block, w_smem<1>(), st, af, w, bias, none, of, (int)M,
+                                                     K, N, relu, g0, os, none);
+  }
 }
 
 template <bool HAS_A, int KIND2, int CN, int RMC = 1, int PL = 3>
 static int launch_chain(const ChainArgs& p, hipStream_t st) {
-  auto kern = bottleneck_chain_kernel<HAS_A, KIND2, CN, RMC, PL>;
   // (the 256-row 64-column body: ring of 3 x 22 KiB)
   constexpr int smem = RMC == 2 ? (3 * (2 * QBM * 64 + 3 * 64 * 32) > W_SMEM ? 3 * (2 * QBM * 64 + 3 * 64 * 32) : W_SMEM) : W_SMEM;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "bottleneck_chain: cannot raise dynamic LDS limit");
-    attr_set = true;
-  }
   constexpr int CBM = QBM * RMC;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((p.M + CBM - 1) / CBM)), dim3(256), smem, st, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch_lds<bottleneck_chain_kernel<HAS_A, KIND2, CN, RMC, PL>>(
+      "bottleneck_chain: cannot raise dynamic LDS limit", dim3((unsigned)((p.M + CBM - 1) / CBM)), dim3(256), smem, st, p);
 }
 
 template <int PL>
@@ -2428,7 +2353,8 @@ static int bottleneck_chain_go(const float* c1, const void* w2_planes, const flo
     return pave_internal_fail(PAVE_E_ARG, "bottleneck_chain: a2 [M, k2] (k2 %% 32 == 0) replaces the residual");
   if ((w1n_planes != nullptr) != (cn > 0) || (w1n_planes && (!c1n || (cn != 64 && cn != 128))))
     return pave_internal_fail(PAVE_E_ARG, "bottleneck_chain: next conv1 with 64 or 128 output channels, or none");
-  if (pave_internal_diag_variant() == 9)
+  const int dvc = pave_internal_diag_variant();
+  if (dvc == PAVE_DV_FIRST_GEN)
     return pave_internal_fail(PAVE_E_UNSUPPORTED, "bottleneck_chain: LDS-DMA generation only");
   ChainArgs p{c1, static_cast<const uint16_t*>(w2_planes), b2, c2,
               static_cast<const uint16_t*>(w3_planes), b3, residual, a2, out,
@@ -2445,9 +2371,8 @@ static int bottleneck_chain_go(const float* c1, const void* w2_planes, const flo
   if (cn == 128) return launch_chain<HA, 0, 128, 1, PL>(p, st);               \
   return launch_chain<HA, 0, 0, 1, PL>(p, st)
   // from two 256-row tiles per block slot of the chip on: 256-row tiles (the 3x3 and a 64-output conv1 with two
-  // row tiles per wave); diag variant 15: never, 16: always
-  const int dvc = pave_internal_diag_variant();
-  if (c1 && cn > 0 && dvc != 15 && (p.M >= 256 * 1024 || dvc == 16)) {
+  // row tiles per wave); PAVE_DV_RM2_NEVER / PAVE_DV_RM2_ALWAYS: never / always
+  if (c1 && cn > 0 && dvc != PAVE_DV_RM2_NEVER && (p.M >= 256 * 1024 || dvc == PAVE_DV_RM2_ALWAYS)) {
     if (a2) {
       if (cn == 64) return launch_chain<true, 4, 64, 2, PL>(p, st);
       return launch_chain<true, 4, 128, 2, PL>(p, st);
@@ -2492,12 +2417,11 @@ extern "C" int pave_bottleneck_chain_f32(const float* c1, const void* w2_planes,
                                          const float* a2, int k2, float* out, const void* w1n_planes,
                                          const float* b1n, float* c1n, int cn, int N, int H, int W,
                                          int nplanes, void* stream) {
-  if (nplanes == PAVE_PLANES_FP16)
-    return bottleneck_chain_go<1>(c1, w2_planes, b2, c2, w3_planes, b3, residual, a2, k2, out, w1n_planes, b1n, c1n,
-                                  cn, N, H, W, stream);
-  if (nplanes != 3) return pave_internal_fail(PAVE_E_ARG, "bottleneck_chain: nplanes must be 3 or PAVE_PLANES_FP16");
-  return bottleneck_chain_go<3>(c1, w2_planes, b2, c2, w3_planes, b3, residual, a2, k2, out, w1n_planes, b1n, c1n,
-                                cn, N, H, W, stream);
+  // (q_planes: 0 for any other nplanes, which the helper refuses)
+  return pave_with_planes(q_planes(nplanes), "bottleneck_chain: nplanes must be 3 or PAVE_PLANES_FP16", [&](auto pl) {
+    return bottleneck_chain_go<decltype(pl)::value>(c1, w2_planes, b2, c2, w3_planes, b3, residual, a2, k2, out,
+                                                    w1n_planes, b1n, c1n, cn, N, H, W, stream);
+  });
 }
 
 // Stem: w_stem = the 11-slab (c, ky, kx' = kx + 1) planes [11][3][64][16]; requires pitch % 4 == 0 and
@@ -2515,15 +2439,11 @@ int pave_internal_stem7x7_q(const float* x, const void* w_stem, const float* bia
 #endif
   constexpr int R = PAVE_STEM_ROWS;
   const long long g2 = (long long)N * ((Ho + R - 1) / R) * ((Wo + SBM - 1) / SBM);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const uint16_t* w = static_cast<const uint16_t*>(w_stem);
   if (planes == 1)
-    hipLaunchKernelGGL((stem7x7_qr_kernel<R, 1>), dim3((unsigned)g2), dim3(192), StemRows<R>::WIN,
-                       reinterpret_cast<hipStream_t>(stream), x, static_cast<const uint16_t*>(w_stem), bias,
-                       y, H, pitch, Ho, Wo, relu);
-  else
-    hipLaunchKernelGGL((stem7x7_qr_kernel<R, 3>), dim3((unsigned)g2), dim3(192), StemRows<R>::WIN,
-                       reinterpret_cast<hipStream_t>(stream), x, static_cast<const uint16_t*>(w_stem), bias,
-                       y, H, pitch, Ho, Wo, relu);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+    return pave_launch<stem7x7_qr_kernel<R, 1>>(dim3((unsigned)g2), dim3(192), StemRows<R>::WIN, st, x, w, bias, y, H,
+                                                pitch, Ho, Wo, relu);
+  return pave_launch<stem7x7_qr_kernel<R, 3>>(dim3((unsigned)g2), dim3(192), StemRows<R>::WIN, st, x, w, bias, y, H,
+                                              pitch, Ho, Wo, relu);
 }

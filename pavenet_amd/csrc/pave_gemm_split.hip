@@ -548,42 +548,17 @@ int g_diag_variant = 0;
 #else
 constexpr int g_diag_variant = 0;   // the shipped library has no kernel-form global
 #endif
-                         // -DPAVE_DIAG build only (pave_diag_gemm_variant): 2 = the 256-row tile forms,
-                         // 3 = 128 x 256 / 8-wave tiles wherever N % 256 == 0, 4 = never,
-                         // 9 = first-generation kernels for every 3-plane form (A/B against
-                         // the LDS-DMA generation of pave_gemm_dma.hip, the default),
-                         // 5 = 3x3 form with 64-bit lane addresses (not buffer-addressed),
-                         // 6 = no split-K plan,
-                         // 13 / 14 = LayerNorm-epilogue GEMM: always the 8-wave / the wide form,
-                         // 8 = LDS-DMA generation without its wide tile form, 7 = wide
-                         // tile form wherever it applies (default: from 512 tiles up),
-                         // 18 = Swin window attention on the per-lane (LDS broadcast) form instead of the
-                         // fp32-MFMA form (pave_decoder.hip),
-                         // 15 / 16 = two row tiles per wave (256-row blocks) for the 64- / 96-column
-                         // tile forms and the ResNet layer1 chain: never / wherever the form exists,
-                         // 17 = no half-tail form (33 .. 48 output columns of a 3x3 as zero-padded 32x32x16
-                         // products instead of 16x16x32 products over slab pairs),
-                         // 19 = the small-row selection of rounds 4 - 5 (no K-split small-row form: the forms the
-                         // bit-equality tests compare), 20 = the wide GEMM capped at one block per CU (40 KiB of
-                         // unused dynamic LDS; tools/coresidency_probe.py), 21 = form policy 2 keeps
-                         // gemm_sk_kernel above 2 048 rows (no multi-tile K-split form: the bit-equality test)
+// (the variants: enum PaveDiag in pave_internal.h)
 
-// Shapes that take the 128 x 256, 8-wave tile (measured per shape, tools/bench_gemm_shapes.py)
-bool use_w8(long long M, int K, int N) {
-  if (N % 256 != 0 || g_diag_variant == 4 || g_diag_variant == 2) return false;
-  if (g_diag_variant == 3) return true;
-  (void)M;
-  (void)K;
-  return false;
-}
+// The 128 x 256, 8-wave tile: a diagnostic-only choice (PAVE_DV_W8_ALWAYS) -- no shape of the model takes it by
+// measurement (tools/bench_gemm_shapes.py)
+bool use_w8(int N) { return N % 256 == 0 && g_diag_variant == PAVE_DV_W8_ALWAYS; }
 
 template <int TM, int TN, bool ABIAS, int P, bool F16, int CONV, bool OCC2 = (P == 1), int WGN = 2,
           bool LNORM = false>
 int launch_gemm(const float* a, const uint16_t* w, const float* bias, const float* residual,
                 float* out, long long M, int K, int N, int relu, const float* a_bias,
-                hipStream_t st, const ConvGeom g = ConvGeom{0, 0, 0, 0, 0, 0},
-                const OutSplit os = OutSplit{nullptr, 0, 0},
-                const LnArgs ln = LnArgs{nullptr, nullptr, 0.f}) {
+                hipStream_t st, const ConvGeom g = {}, const OutSplit os = {}, const LnArgs ln = {}) {
   constexpr int NT = 128 * WGN, NW = 2 * WGN;
   constexpr int BM = 2 * TM * 32, BN = WGN * TN * 32;
   constexpr int EPI = NW * 32 * (TN * 32 + 4) * 4 + (LNORM ? 2 * BM * WGN * 4 : 0);
@@ -593,22 +568,24 @@ int launch_gemm(const float* a, const uint16_t* w, const float* bias, const floa
   if (gx >= (1ll << 31)) return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3: grid too large");
   using kern_t = void (*)(const float*, const uint16_t*, const float*, const float*, float*, int, int,
                           int, int, const float*, ConvGeom, OutSplit, LnArgs);
-  kern_t kern;
-  if constexpr (WGN == 4) kern = gemm_bf16x3_kernel_w8<TM, TN, ABIAS, P, CONV, LNORM>;
-  else if constexpr (OCC2) kern = gemm_bf16x3_kernel_occ2<TM, TN, ABIAS, P, F16, CONV>;
-  else kern = gemm_bf16x3_kernel<TM, TN, ABIAS, P, F16, CONV>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-      return pave_internal_fail(PAVE_E_LAUNCH, "gemm_bf16x3: cannot raise dynamic LDS limit");
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(NT), SMEM, st, a, w, bias, residual, out,
-                     (int)M, K, N, relu, a_bias, g, os, ln);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  constexpr kern_t kern = [] {
+    if constexpr (WGN == 4) return gemm_bf16x3_kernel_w8<TM, TN, ABIAS, P, CONV, LNORM>;
+    else if constexpr (OCC2) return gemm_bf16x3_kernel_occ2<TM, TN, ABIAS, P, F16, CONV>;
+    else return gemm_bf16x3_kernel<TM, TN, ABIAS, P, F16, CONV>;
+  }();
+  return pave_launch_lds<kern>("gemm_bf16x3: cannot raise dynamic LDS limit", dim3((unsigned)gx), dim3(NT), SMEM, st, a,
+                               w, bias, residual, out, (int)M, K, N, relu, a_bias, g, os, ln);
+}
+
+// What every call of the LDS-DMA generation (pave_internal_gemm_q) shares: N output columns (out / bias /
+// residual) on weight planes padded to 64 rows; the callers name the rest.
+GemmQ gemm_q_call(const float* a, const void* w_planes, const float* bias, const float* residual, float* out,
+                  long long M, int K, int N, int relu, int nplanes, void* stream) {
+  GemmQ q;
+  q.a = a, q.w_planes = w_planes, q.bias = bias, q.residual = residual, q.out = out;
+  q.M = M, q.K = K, q.N = (N + 63) / 64 * 64, q.n_real = N, q.relu = relu;
+  q.planes = q_planes(nplanes), q.stream = stream;
+  return q;
 }
 
 }  // namespace
@@ -621,19 +598,13 @@ int pave_split_bf16x3_f32(const float* x, void* planes, long long n, int nplanes
   if (!x || !planes || n <= 0 || nplanes < 1 || nplanes > 3)
     return pave_internal_fail(PAVE_E_ARG, "split_bf16x3: bad argument (1 <= nplanes <= 3)");
   const long long nb = (n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536;
-  hipLaunchKernelGGL(split_bf16x3_kernel, dim3((unsigned)nb), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, static_cast<uint16_t*>(planes), n,
-                     nplanes, f16);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pave_internal_fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<split_bf16x3_kernel>(dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
+                                          static_cast<uint16_t*>(planes), n, nplanes, f16);
 }
 
 static int gemm_split_entry(const float* a, const float* a_bias, const void* w_planes,
                             const float* bias, const float* residual, float* out, long long M,
                             int K, int N, int relu, int nplanes, void* stream, OutSplit os);
-// nplanes of the C ABI -> the LDS-DMA generation's operand planes (3 | 1 = fp16), 0 = not one of its modes
-static inline int q_planes(int nplanes) { return nplanes == 3 ? 3 : (nplanes == PAVE_PLANES_FP16 ? 1 : 0); }
 
 int pave_gemm_bf16x3_encproj_f32(const float* a, const void* w_planes, const float* table,
                                  long long table_rows, const float* value_bias, const float* ref,
@@ -651,8 +622,7 @@ int pave_gemm_bf16x3_encproj_f32(const float* a, const void* w_planes, const flo
 int pave_gemm_bf16x3_f32(const float* a, const float* a_bias, const void* w_planes,
                          const float* bias, const float* residual, float* out, long long M, int K,
                          int N, int relu, int nplanes, void* stream) {
-  return gemm_split_entry(a, a_bias, w_planes, bias, residual, out, M, K, N, relu, nplanes, stream,
-                          OutSplit{nullptr, 0, 0});
+  return gemm_split_entry(a, a_bias, w_planes, bias, residual, out, M, K, N, relu, nplanes, stream, OutSplit{});
 }
 
 int pave_gemm_bf16x3_ex_f32(const float* a, const float* a_bias, const void* w_planes,
@@ -674,18 +644,19 @@ static int gemm_split_entry(const float* a, const float* a_bias, const void* w_p
                             const float* bias, const float* residual, float* out, long long M,
                             int K, int N, int relu, int nplanes, void* stream, OutSplit os) {
   if (!a || !w_planes || !out) return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3: null pointer");
-  if (relu < 0 || relu > 3 || (relu >= 2 && (!q_planes(nplanes) || g_diag_variant == 9)))
+  if (relu < 0 || relu > 3 || (relu >= 2 && (!q_planes(nplanes) || g_diag_variant == PAVE_DV_FIRST_GEN)))
     return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3: relu = 0 | 1 | 2 | 3 (2 = exact GELU, 3 = sigmoid: 3 planes / fp16 only)");
   if (M <= 0 || K <= 0 || N <= 0 || M >= (1ll << 31))
     return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3: bad sizes (0 < M < 2^31)");
   // 3 planes (the exact split): the LDS-DMA generation (pave_gemm_dma.hip) takes K %% 32 == 0 and any
   // N %% 4 == 0 -- the weight planes then carry roundup(N, 64) rows (zero rows beyond N), out / bias /
   // residual have N columns.  The kernels of this file keep the 1- / 2-plane and fp16 modes.
-  if (q_planes(nplanes) && g_diag_variant != 9 && K % 32 == 0 && K >= 64 && N % 4 == 0 &&
-      (N % 64 == 0 || !os.out2))
-    return pave_internal_gemm_q(a, a_bias, w_planes, bias, residual, os.res_rows, out, os.out2, os.nsplit,
-                                M, K, (N + 63) / 64 * 64, relu, 0, 0, 0, 0, 0, 0, 0, stream, nullptr, N, 1, 0,
-                                q_planes(nplanes));
+  if (q_planes(nplanes) && g_diag_variant != PAVE_DV_FIRST_GEN && K % 32 == 0 && K >= 64 && N % 4 == 0 &&
+      (N % 64 == 0 || !os.out2)) {
+    GemmQ q = gemm_q_call(a, w_planes, bias, residual, out, M, K, N, relu, nplanes, stream);
+    q.a_bias = a_bias, q.residual_rows = os.res_rows, q.out2 = os.out2, q.n_split = os.nsplit;
+    return pave_internal_gemm_q(q);
+  }
   if (K % 64 != 0 || (N % 128 != 0 && !(N == 64 && nplanes == 3 && !os.out2)))
     return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3: K %% 64 == 0 and N %% 128 == 0 (or N == 64 "
                                           "with 3 planes) required");
@@ -693,24 +664,23 @@ static int gemm_split_entry(const float* a, const float* a_bias, const void* w_p
     return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3: nplanes must be 1, 2, 3 or PAVE_PLANES_FP16");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const uint16_t* w = static_cast<const uint16_t*>(w_planes);
+  const ConvGeom g0{};
   if (N == 64) {  // 128 x 64 tiles (the ResNet layer1 1x1 reductions): HBM-bound, A read once
-    const ConvGeom gz{0, 0, 0, 0, 0, 0};
     if (a_bias)
-      return launch_gemm<2, 1, true, 3, false, 0, true>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, gz, os);
-    return launch_gemm<2, 1, false, 3, false, 0, true>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, gz, os);
+      return launch_gemm<2, 1, true, 3, false, 0, true>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g0, os);
+    return launch_gemm<2, 1, false, 3, false, 0, true>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g0, os);
   }
   // P = 3: 128 x 128 tiles, two workgroups (8 waves) per CU -- one workgroup's operand split
   // (VALU) and LDS traffic overlap the other's MFMAs: 12-25 % faster than the 256 x 128 tile at
   // one wave per SIMD on every shape of the model (tools/bench_gemm_shapes.py)
-  const ConvGeom g0{0, 0, 0, 0, 0, 0};
   // 128 x 256 tile on 8 waves where the shape allows it and it wins (see use_w8)
-  if (nplanes == 3 && use_w8(M, K, N) && (!os.out2 || os.nsplit % 256 == 0)) {
+  if (nplanes == 3 && use_w8(N) && (!os.out2 || os.nsplit % 256 == 0)) {
     if (a_bias)
       return launch_gemm<2, 2, true, 3, false, false, true, 4>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g0, os);
     return launch_gemm<2, 2, false, 3, false, false, true, 4>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g0, os);
   }
 #define PAVE_GO(AB, P) \
-  return (P == 3 && g_diag_variant != 2) \
+  return (P == 3 && g_diag_variant != PAVE_DV_TILE256) \
       ? launch_gemm<2, 2, AB, P, false, false, true>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g0, os) \
       : launch_gemm<4, 2, AB, P, false, false>(a, w, bias, residual, out, M, K, N, relu, a_bias, st, g0, os)
   if (nplanes == PAVE_PLANES_FP16) {
@@ -731,7 +701,7 @@ static int gemm_split_entry(const float* a, const float* a_bias, const void* w_p
 // Split-K form of the plain row GEMM (few row tiles, K >= 2048: ResNet layer4's 1x1 reductions and the neck's
 // C5 lateral on a one-clip batch).  The plan is pave_internal_splitk_plan's -- the 3x3 form's.
 long long pave_gemm_splitk_workspace_bytes(long long M, int K, int N) {
-  if (M <= 0 || M >= (1ll << 31) || K < 64 || K % 32 != 0 || N <= 0 || N % 4 != 0 || g_diag_variant == 9) return 0;
+  if (M <= 0 || M >= (1ll << 31) || K < 64 || K % 32 != 0 || N <= 0 || N % 4 != 0 || g_diag_variant == PAVE_DV_FIRST_GEN) return 0;
   int parts, per;
   pave_internal_splitk_plan(M, K, (N + 63) / 64 * 64, &parts, &per);
   return parts > 1 ? (long long)parts * M * N * 4 : 0;
@@ -747,12 +717,12 @@ int pave_gemm_bf16x3_splitk_f32(const float* a, const void* w_planes, const floa
   if (need == 0 || workspace_bytes < need)
     return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3_splitk: shape has no split-K plan (use pave_gemm_bf16x3_f32) or "
                                           "the workspace is smaller than pave_gemm_splitk_workspace_bytes");
-  const int Np = (N + 63) / 64 * 64;
   int parts, per;
-  pave_internal_splitk_plan(M, K, Np, &parts, &per);
+  pave_internal_splitk_plan(M, K, (N + 63) / 64 * 64, &parts, &per);
   float* ws = static_cast<float*>(workspace);
-  const int rc = pave_internal_gemm_q(a, nullptr, w_planes, nullptr, nullptr, 0, ws, nullptr, 0, M, K, Np, 0, 0, 0, 0,
-                                      0, 0, 0, 0, stream, nullptr, N, parts, per, q_planes(nplanes));
+  GemmQ q = gemm_q_call(a, w_planes, nullptr, nullptr, ws, M, K, N, 0, nplanes, stream);
+  q.ksplit = parts, q.ks_slabs = per;
+  const int rc = pave_internal_gemm_q(q);
   if (rc != PAVE_OK) return rc;
   return pave_internal_splitk_reduce(ws, parts, M, N, bias, residual, relu, out, stream);
 }
@@ -776,8 +746,9 @@ int pave_gemm_bf16x3_cat_f32(const float* a, long long K1, const float* a2, cons
   if (K % 32 != 0 || K < 64 || N % 64 != 0 || K1 <= 0 || K1 >= K || K1 % 16 != 0)
     return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3_cat: K %% 32 == 0, N %% 64 == 0, 0 < K1 < K, K1 %% 16 == 0");
   if (!q_planes(nplanes)) return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3_cat: nplanes must be 3 or PAVE_PLANES_FP16");
-  return pave_internal_gemm_q(a, nullptr, w_planes, bias, residual, 0, out, nullptr, 0, M, K, N, relu, 4,
-                              0, 0, (int)K1, 0, 0, 0, stream, a2, 0, 1, 0, q_planes(nplanes));
+  GemmQ q = gemm_q_call(a, w_planes, bias, residual, out, M, K, N, relu, nplanes, stream);
+  q.rows = GEMMQ_ROWS2, q.a2 = a2, q.k1 = (int)K1;
+  return pave_internal_gemm_q(q);
 }
 
 int pave_gemm_bf16x3_grouped_f32(const float* a, long long lda, const void* w_planes, const float* bias,
@@ -790,11 +761,12 @@ int pave_gemm_bf16x3_grouped_f32(const float* a, long long lda, const void* w_pl
       lda < (long long)(N / group_n) * K || lda % 4 != 0 || lda >= (1ll << 23))
     return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3_grouped: K %% 32 == 0, group_n %% 64 == 0, N %% group_n == 0, "
                                           "groups * K <= lda < 2^23 (a tile's 127 rows x lda x 4 B is a 32-bit lane offset), lda %% 4 == 0");
-  // column tiles must not straddle a group: 128-wide tiles need group_n %% 128 == 0
-  const int np = (N % 128 == 0 && group_n % 128 == 0) ? N : -N;
   if (!q_planes(nplanes)) return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3_grouped: nplanes must be 3 or PAVE_PLANES_FP16");
-  return pave_internal_gemm_q(a, nullptr, w_planes, bias, nullptr, 0, out, nullptr, 0, M, K, np, relu, 0,
-                              (int)lda, group_n, 0, 0, 0, 0, stream, nullptr, 0, 1, 0, q_planes(nplanes));
+  GemmQ q = gemm_q_call(a, w_planes, bias, nullptr, out, M, K, N, relu, nplanes, stream);
+  q.lda = (int)lda, q.group_n = group_n;
+  // column tiles must not straddle a group: 128-wide tiles need group_n %% 128 == 0
+  q.narrow_groups = !(N % 128 == 0 && group_n % 128 == 0);
+  return pave_internal_gemm_q(q);
 }
 
 int pave_gemm_bf16x3_ln_f32(const float* a, const void* w_planes, const float* bias,
@@ -807,13 +779,12 @@ int pave_gemm_bf16x3_ln_f32(const float* a, const void* w_planes, const float* b
   if (K % 64 != 0 || N != 256)
     return pave_internal_fail(PAVE_E_UNSUPPORTED, "gemm_bf16x3_ln: K %% 64 == 0 and N == 256 required");
   if (!q_planes(nplanes)) return pave_internal_fail(PAVE_E_ARG, "gemm_bf16x3_ln: nplanes must be 3 or PAVE_PLANES_FP16");
-  if (g_diag_variant != 9 || nplanes != 3)
+  if (g_diag_variant != PAVE_DV_FIRST_GEN || nplanes != 3)
     return pave_internal_gemm_q_ln(a, w_planes, bias, residual, gamma, beta, eps, out, M, K, N, stream,
                                    q_planes(nplanes));
   return launch_gemm<2, 2, false, 3, false, false, true, 4, true>(
       a, static_cast<const uint16_t*>(w_planes), bias, residual, out, M, K, N, 0, nullptr,
-      reinterpret_cast<hipStream_t>(stream), ConvGeom{0, 0, 0, 0, 0, 0}, OutSplit{nullptr, 0, 0},
-      LnArgs{gamma, beta, eps});
+      reinterpret_cast<hipStream_t>(stream), ConvGeom{}, OutSplit{}, LnArgs{gamma, beta, eps});
 }
 
 #ifdef PAVE_DIAG
@@ -833,7 +804,7 @@ int pave_conv3x3_split_f32(const float* x, const void* w_planes, const float* bi
     return pave_internal_fail(PAVE_E_ARG, "conv3x3_split: bad sizes (stride 1 or 2; relu 0 | 1)");
   const bool padded = Cin % 64 != 0 || Cout % 64 != 0;   // zero-padded weight planes: 3-plane DMA kernel only
   if (Cin <= 0 || Cout <= 0 || Cin % 16 != 0 || Cout % 4 != 0 ||
-      ((padded || residual) && (!q_planes(nplanes) || g_diag_variant == 9)))
+      ((padded || residual) && (!q_planes(nplanes) || g_diag_variant == PAVE_DV_FIRST_GEN)))
     return pave_internal_fail(PAVE_E_ARG, "conv3x3_split: Cin %% 16 == 0 and Cout %% 4 == 0 (3 planes; the other "
                                           "modes: Cin, Cout %% 64 == 0, no residual) required");
   if ((nplanes < 1 || nplanes > 3) && nplanes != PAVE_PLANES_FP16)
@@ -842,16 +813,17 @@ int pave_conv3x3_split_f32(const float* x, const void* w_planes, const float* bi
   const long long M = (long long)N * Ho * Wo;
   if (M >= (1ll << 31) || (long long)N * H * W * Cin >= (1ll << 40))
     return pave_internal_fail(PAVE_E_ARG, "conv3x3_split: tensor too large");
-  if (q_planes(nplanes) && g_diag_variant != 9)   // K = 9 Cin padded to a multiple of 32, Cout to one of 64
-    return pave_internal_gemm_q(x, nullptr, w_planes, bias, residual, 0, y, nullptr, 0, M,
-                                (9 * Cin + 31) / 32 * 32, (Cout + 63) / 64 * 64, relu, 1, H, W, Cin, Ho,
-                                Wo, stride, stream, nullptr, Cout, 1, 0, q_planes(nplanes));
+  if (q_planes(nplanes) && g_diag_variant != PAVE_DV_FIRST_GEN) {   // K = 9 Cin padded to a multiple of 32
+    GemmQ q = gemm_q_call(x, w_planes, bias, residual, y, M, (9 * Cin + 31) / 32 * 32, Cout, relu, nplanes, stream);
+    q.rows = GEMMQ_CONV3X3, q.H = H, q.W = W, q.Cin = Cin, q.Ho = Ho, q.Wo = Wo, q.stride = stride;
+    return pave_internal_gemm_q(q);
+  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const uint16_t* w = static_cast<const uint16_t*>(w_planes);
   const ConvGeom g{H, W, Cin, Ho, Wo, stride};
   const int K = 9 * Cin;
 #define PAVE_CV(TN_, P_, F_) \
-  return (P_ == 3 && g_diag_variant != 2) \
+  return (P_ == 3 && g_diag_variant != PAVE_DV_TILE256) \
       ? launch_gemm<2, TN_, false, P_, F_, true, true>(x, w, bias, nullptr, y, M, K, Cout, relu, nullptr, st, g) \
       : launch_gemm<4, TN_, false, P_, F_, true>(x, w, bias, nullptr, y, M, K, Cout, relu, nullptr, st, g)
   if (Cout % 128 == 0) {
@@ -869,7 +841,7 @@ int pave_conv3x3_split_f32(const float* x, const void* w_planes, const float* bi
 
 long long pave_conv3x3_splitk_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (stride != 1 && stride != 2) ||
-      Cin % 16 != 0 || Cout % 4 != 0 || g_diag_variant == 9)
+      Cin % 16 != 0 || Cout % 4 != 0 || g_diag_variant == PAVE_DV_FIRST_GEN)
     return 0;
   const long long M = (long long)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);
   int parts, per;
@@ -891,14 +863,15 @@ int pave_conv3x3_splitk_f32(const float* x, const void* w_planes, const float* b
   const long long M = (long long)N * Ho * Wo;
   if ((long long)N * H * W * Cin >= (1ll << 40))
     return pave_internal_fail(PAVE_E_ARG, "conv3x3_splitk: tensor too large");
-  const int Kp = (9 * Cin + 31) / 32 * 32, Np = (Cout + 63) / 64 * 64;
+  const int Kp = (9 * Cin + 31) / 32 * 32;
   int parts, per;
-  pave_internal_splitk_plan(M, Kp, Np, &parts, &per);
+  pave_internal_splitk_plan(M, Kp, (Cout + 63) / 64 * 64, &parts, &per);
   float* ws = static_cast<float*>(workspace);
   if (!q_planes(nplanes)) return pave_internal_fail(PAVE_E_ARG, "conv3x3_splitk: nplanes must be 3 or PAVE_PLANES_FP16");
-  const int rc = pave_internal_gemm_q(x, nullptr, w_planes, nullptr, nullptr, 0, ws, nullptr, 0, M, Kp, Np, 0,
-                                      1, H, W, Cin, Ho, Wo, stride, stream, nullptr, Cout, parts, per,
-                                      q_planes(nplanes));
+  GemmQ q = gemm_q_call(x, w_planes, nullptr, nullptr, ws, M, Kp, Cout, 0, nplanes, stream);
+  q.rows = GEMMQ_CONV3X3, q.H = H, q.W = W, q.Cin = Cin, q.Ho = Ho, q.Wo = Wo, q.stride = stride;
+  q.ksplit = parts, q.ks_slabs = per;
+  const int rc = pave_internal_gemm_q(q);
   if (rc != PAVE_OK) return rc;
   return pave_internal_splitk_reduce(ws, parts, M, Cout, bias, residual, relu, y, stream);
 }
@@ -917,9 +890,11 @@ int pave_conv1x1_strided_split_f32(const float* x, const void* w_planes, const f
     return pave_internal_fail(PAVE_E_ARG, "conv1x1_strided_split: tensor too large");
   // (the LDS-DMA kernel addresses the strided pixels with 32-bit byte offsets from x)
   if (!q_planes(nplanes)) return pave_internal_fail(PAVE_E_ARG, "conv1x1_strided_split: nplanes must be 3 or PAVE_PLANES_FP16");
-  if ((g_diag_variant != 9 || nplanes != 3) && (long long)N * H * W * Cin * 4 < (1ll << 32))
-    return pave_internal_gemm_q(x, nullptr, w_planes, bias, nullptr, 0, y, nullptr, 0, M, Cin, Cout, relu,
-                                3, H, W, Cin, Ho, Wo, stride, stream, nullptr, 0, 1, 0, q_planes(nplanes));
+  if ((g_diag_variant != PAVE_DV_FIRST_GEN || nplanes != 3) && (long long)N * H * W * Cin * 4 < (1ll << 32)) {
+    GemmQ q = gemm_q_call(x, w_planes, bias, nullptr, y, M, Cin, Cout, relu, nplanes, stream);
+    q.rows = GEMMQ_CONV1X1S, q.H = H, q.W = W, q.Cin = Cin, q.Ho = Ho, q.Wo = Wo, q.stride = stride;
+    return pave_internal_gemm_q(q);
+  }
   if (nplanes != 3) return pave_internal_fail(PAVE_E_UNSUPPORTED, "conv1x1_strided_split: fp16 operands need a map below 4 GiB");
   const ConvGeom g{H, W, Cin, Ho, Wo, stride};
   return launch_gemm<2, 2, false, 3, false, 0, true>(x, static_cast<const uint16_t*>(w_planes), bias,
@@ -947,7 +922,7 @@ int pave_conv7x7s2_nchw_split_f32(const float* x, const void* w_planes, const fl
   // (c, ky, kx | pad) for the kernel of this file, then 11 slabs (c, ky, kx + 1) for the LDS-window
   // kernel of pave_gemm_dma.hip, which needs 16-byte aligned image rows
   if (!q_planes(nplanes)) return pave_internal_fail(PAVE_E_ARG, "conv7x7s2_nchw_split: nplanes must be 3 or PAVE_PLANES_FP16");
-  if ((g_diag_variant != 9 || nplanes != 3 || row_pitch != W) && row_pitch % 4 == 0 &&
+  if ((g_diag_variant != PAVE_DV_FIRST_GEN || nplanes != 3 || row_pitch != W) && row_pitch % 4 == 0 &&
       (reinterpret_cast<uintptr_t>(x) & 15) == 0)
     return pave_internal_stem7x7_q(x, static_cast<const uint16_t*>(w_planes) + 12 * q_planes(nplanes) * 64 * 16, bias, y,
                                    N, H, W, row_pitch, relu, stream, q_planes(nplanes));

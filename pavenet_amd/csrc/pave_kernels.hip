@@ -907,10 +907,7 @@ int launch_enc_head_major_t(const FusedParams& p0, hipStream_t stream) {
   const int npatch = (p.n_units + 31) / 32;
   const int nb = ((npatch + PATCHES - 1) / PATCHES) * 8;
   p.n_blocks_logical = nb;
-  hipLaunchKernelGGL((enc_head_major_kernel<PATCHES, UNR>), dim3(nb), dim3(256), 0, stream, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<enc_head_major_kernel<PATCHES, UNR>>(dim3(nb), dim3(256), 0, stream, p);
 }
 
 int launch_enc_head_major(const FusedParams& p, hipStream_t stream) {
@@ -925,10 +922,7 @@ int launch_fused(const FusedParams& p0, hipStream_t stream) {
   constexpr int kUnitsPerBlock = 4 / WQ;
   const int nb = (p.n_units + kUnitsPerBlock - 1) / kUnitsPerBlock;
   p.n_blocks_logical = nb;
-  hipLaunchKernelGGL((fused_deform_attn_kernel<MODE, PPL, WQ>), dim3(nb), dim3(256), 0, stream, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<fused_deform_attn_kernel<MODE, PPL, WQ>>(dim3(nb), dim3(256), 0, stream, p);
 }
 
 template <typename scalar_t>
@@ -947,7 +941,6 @@ int msda_forward_impl(const scalar_t* value, const int64_t* shapes, const int64_
   const long long n = (long long)bs * Lq * M * D;
   if ((long long)S * M * D * (long long)sizeof(scalar_t) >= (1ll << 31))
     return fail(PAVE_E_ARG, "ms_deform_attn_forward: one value slab must be < 2 GiB");
-  bool launched = false;
   if constexpr (sizeof(scalar_t) == 4) {
     const int G = D / 4;
     const long long ngroups = (long long)bs * Lq * M;
@@ -956,36 +949,29 @@ int msda_forward_impl(const scalar_t* value, const int64_t* shapes, const int64_
       const float* lc = reinterpret_cast<const float*>(loc);
       const float* aw = reinterpret_cast<const float*>(attw);
       float* o = reinterpret_cast<float*>(out);
-#define PAVE_LAUNCH_VEC(GG)                                                                     \
-  {                                                                                             \
-    const long long per = 256 / GG;                                                             \
-    long long nb = (ngroups + per - 1) / per;                                                   \
-    if (nb > 65536 * 4) nb = 65536 * 4;                                                         \
-    hipLaunchKernelGGL((msda_fwd_vec_kernel<GG>), dim3((unsigned)nb), dim3(256), 0, st, ngroups, \
-                       v, shapes, lsi, lc, aw, S, M, D, L, Lq, P, o);                           \
-    launched = true;                                                                            \
-  }
+      const long long per = 256 / G;
+      long long nb = (ngroups + per - 1) / per;
+      if (nb > 65536 * 4) nb = 65536 * 4;
+#define PAVE_LAUNCH_VEC(GG)                                                                            \
+  case GG:                                                                                             \
+    return pave_launch<msda_fwd_vec_kernel<GG>>(dim3((unsigned)nb), dim3(256), 0, st, ngroups, v, shapes, lsi, lc, \
+                                                aw, S, M, D, L, Lq, P, o)
       switch (G) {
-        case 1: PAVE_LAUNCH_VEC(1) break;
-        case 2: PAVE_LAUNCH_VEC(2) break;
-        case 4: PAVE_LAUNCH_VEC(4) break;
-        case 8: PAVE_LAUNCH_VEC(8) break;
-        case 16: PAVE_LAUNCH_VEC(16) break;
-        case 32: PAVE_LAUNCH_VEC(32) break;
-        case 64: PAVE_LAUNCH_VEC(64) break;
+        PAVE_LAUNCH_VEC(1);
+        PAVE_LAUNCH_VEC(2);
+        PAVE_LAUNCH_VEC(4);
+        PAVE_LAUNCH_VEC(8);
+        PAVE_LAUNCH_VEC(16);
+        PAVE_LAUNCH_VEC(32);
+        PAVE_LAUNCH_VEC(64);
       }
 #undef PAVE_LAUNCH_VEC
     }
   }
-  if (!launched) {
-    long long nb = (n + 255) / 256;
-    if (nb > 65536 * 4) nb = 65536 * 4;
-    hipLaunchKernelGGL((msda_fwd_scalar_kernel<scalar_t>), dim3((unsigned)nb), dim3(256), 0, st, n,
-                       value, shapes, lsi, loc, attw, S, M, D, L, Lq, P, out);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  long long nb = (n + 255) / 256;
+  if (nb > 65536 * 4) nb = 65536 * 4;
+  return pave_launch<msda_fwd_scalar_kernel<scalar_t>>(dim3((unsigned)nb), dim3(256), 0, st, n, value, shapes, lsi,
+                                                       loc, attw, S, M, D, L, Lq, P, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1082,31 +1068,25 @@ int msda_backward_impl(const scalar_t* value, const int64_t* shapes, const int64
     return fail(PAVE_E_STEP, "ms_deform_attn_backward: batch must be divisible by im2col_step");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long long ngroups = (long long)bs * Lq * M;
-  bool done = false;
-#define PAVE_BWD(T_, G_, C_)                                                                     \
-  {                                                                                               \
-    long long nb = (ngroups + (256 / G_) - 1) / (256 / G_);                                       \
-    if (nb > 65536 * 4) nb = 65536 * 4;                                                           \
-    hipLaunchKernelGGL((msda_bwd_kernel<T_, G_, C_>), dim3((unsigned)nb), dim3(256), 0, st,      \
-                       ngroups, value, shapes, lsi, loc, attw, gout, S, M, D, L, Lq, P, gvalue,   \
-                       gloc, gattw);                                                              \
-    done = true;                                                                                  \
-  }
+  const auto blocks = [&](int g) {   // 256 / g lane groups per block
+    const long long nb = (ngroups + (256 / g) - 1) / (256 / g);
+    return dim3((unsigned)(nb > 65536 * 4 ? 65536 * 4 : nb));
+  };
+#define PAVE_BWD(T_, G_, C_)                                                                                  \
+  return pave_launch<msda_bwd_kernel<T_, G_, C_>>(blocks(G_), dim3(256), 0, st, ngroups, value, shapes, lsi, loc, \
+                                                  attw, gout, S, M, D, L, Lq, P, gvalue, gloc, gattw)
   if constexpr (sizeof(scalar_t) == 4) {
     if (D % 4 == 0) {
       const int G = D / 4;
-      if (G == 8) PAVE_BWD(float, 8, 4)
-      else if (G == 16) PAVE_BWD(float, 16, 4)
-      else if (G == 4) PAVE_BWD(float, 4, 4)
-      else if (G == 2) PAVE_BWD(float, 2, 4)
-      else if (G == 1) PAVE_BWD(float, 1, 4)
+      if (G == 8) PAVE_BWD(float, 8, 4);
+      if (G == 16) PAVE_BWD(float, 16, 4);
+      if (G == 4) PAVE_BWD(float, 4, 4);
+      if (G == 2) PAVE_BWD(float, 2, 4);
+      if (G == 1) PAVE_BWD(float, 1, 4);
     }
   }
-  if (!done) PAVE_BWD(scalar_t, 1, 1)
+  PAVE_BWD(scalar_t, 1, 1);
 #undef PAVE_BWD
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1717,6 +1697,20 @@ __global__ __launch_bounds__(256) void conv3x3s2_c3_kernel(const float* __restri
   }
 }
 
+// What the two fused sampler entries share; they name their units and points per level themselves
+FusedParams fused_params(const float* value, const int64_t* spatial_shapes, const int64_t* level_start,
+                         const float* proj, const float* ref, float* out, float* stat_max, float* stat_sum,
+                         int n_clips, int T, int S, int L, int proj_stride, const int32_t* frame_table, int n_slabs,
+                         int ref_levels) {
+  FusedParams p{};
+  p.value = value, p.shapes = spatial_shapes, p.lsi = level_start, p.proj = proj, p.ref = ref;
+  p.frame_table = frame_table;
+  p.n_slabs = frame_table ? n_slabs : n_clips * T;
+  p.out = out, p.stat_max = stat_max, p.stat_sum = stat_sum;
+  p.T = T, p.S = S, p.L = L, p.ref_L = ref_levels, p.proj_stride = proj_stride;
+  return p;
+}
+
 }  // namespace
 
 int pave_internal_fail(int code, const char* msg) { return fail(code, msg); }
@@ -1768,27 +1762,10 @@ int pave_deform_attn_grid_fused_f32(const float* value, const int64_t* spatial_s
     return fail(PAVE_E_ARG, "deform_attn_grid_fused: one value slab must be < 2 GiB");
   if (!unit_clip && (long long)n_clips * units_per_clip < n_units)
     return fail(PAVE_E_ARG, "deform_attn_grid_fused: n_units exceeds n_clips * units_per_clip");
-  FusedParams p{};
-  p.value = value;
-  p.shapes = spatial_shapes;
-  p.lsi = level_start;
-  p.proj = proj;
-  p.ref = ref;
-  p.unit_clip = unit_clip;
-  p.order = order;
-  p.frame_table = frame_table;
-  p.n_slabs = frame_table ? n_slabs : n_clips * T;
-  p.out = out;
-  p.stat_max = stat_max;
-  p.stat_sum = stat_sum;
-  p.n_units = n_units;
-  p.units_per_clip = units_per_clip;
-  p.T = T;
-  p.S = S;
-  p.L = L;
-  p.P = P;
-  p.ref_L = ref_levels;
-  p.proj_stride = proj_stride;
+  FusedParams p = fused_params(value, spatial_shapes, level_start, proj, ref, out, stat_max, stat_sum, n_clips, T, S,
+                               L, proj_stride, frame_table, n_slabs, ref_levels);
+  p.unit_clip = unit_clip, p.order = order;
+  p.n_units = n_units, p.units_per_clip = units_per_clip, p.P = P;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (T == 1 && P == 4 && L <= 4) {
     // head-major split; its float4 / float2 projection loads need 16-byte aligned rows, other
@@ -1824,27 +1801,9 @@ int pave_deform_attn_pose_fused_f32(const float* value, const int64_t* spatial_s
     return fail(PAVE_E_ARG, "deform_attn_pose_fused: proj_stride too small");
   if ((long long)S * kRowFloats * 4 >= (1ll << 31))
     return fail(PAVE_E_ARG, "deform_attn_pose_fused: one value slab must be < 2 GiB");
-  FusedParams p{};
-  p.value = value;
-  p.shapes = spatial_shapes;
-  p.lsi = level_start;
-  p.proj = proj;
-  p.ref = ref;
-  p.unit_clip = nullptr;
-  p.order = nullptr;
-  p.frame_table = frame_table;
-  p.n_slabs = frame_table ? n_slabs : n_clips * T;
-  p.out = out;
-  p.stat_max = stat_max;
-  p.stat_sum = stat_sum;
-  p.n_units = n_clips * Q;
-  p.units_per_clip = Q;
-  p.T = T;
-  p.S = S;
-  p.L = L;
-  p.P = K;
-  p.ref_L = ref_levels;
-  p.proj_stride = proj_stride;
+  FusedParams p = fused_params(value, spatial_shapes, level_start, proj, ref, out, stat_max, stat_sum, n_clips, T, S,
+                               L, proj_stride, frame_table, n_slabs, ref_levels);
+  p.n_units = n_clips * Q, p.units_per_clip = Q, p.P = K;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (K <= 16) return launch_fused<kPose, 2, 4>(p, st);
   return launch_fused<kPose, 3, 4>(p, st);
@@ -1861,11 +1820,8 @@ int pave_oks_nms_f32(const float* kpts, const float* scores, const double* sigma
   const size_t stage = (size_t)N * K * 2 * sizeof(float) + (size_t)K * sizeof(double);
   const int staged = shmem + stage <= 48 * 1024;   // (100 poses x 15 key points: 12 KB)
   if (staged) shmem += stage;
-  hipLaunchKernelGGL(oks_nms_kernel, dim3(n_clips), dim3(256), shmem, st, kpts, scores, sigmas,
-                     thresh, keep, order, N, K, staged);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<oks_nms_kernel>(
+      dim3(n_clips), dim3(256), shmem, st, kpts, scores, sigmas, thresh, keep, order, N, K, staged);
 }
 
 int pave_fill_rows_f32(float* x, long long ld, long long total_rows, const int* rows, long long n_rows,
@@ -1877,11 +1833,9 @@ int pave_fill_rows_f32(float* x, long long ld, long long total_rows, const int* 
   const long long n4 = n_rows * (C >> 2);
   long long nb = (n4 + 255) / 256;
   if (nb > 256 * 16) nb = 256 * 16;
-  hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     x, ld, rows, n4, C >> 2, total_rows, values);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<fill_rows_kernel>(
+      dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, ld, rows, n4, C >> 2, total_rows,
+      values);
 }
 
 int pave_repitch_rows_f32(const float* src, float* dst, long long rows, int W, int pitch, void* stream) {
@@ -1891,11 +1845,8 @@ int pave_repitch_rows_f32(const float* src, float* dst, long long rows, int W, i
   const long long n4 = rows * (pitch >> 2);
   long long nb = (n4 + 255) / 256;
   if (nb > 256 * 32) nb = 256 * 32;
-  hipLaunchKernelGGL(repitch_rows_kernel, dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     src, dst, rows, W, pitch >> 2);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<repitch_rows_kernel>(
+      dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, dst, rows, W, pitch >> 2);
 }
 
 int pave_bias_act_rows_f32(const float* x, const float* bias, const float* res, float* y,
@@ -1905,11 +1856,8 @@ int pave_bias_act_rows_f32(const float* x, const float* bias, const float* res, 
   const long long n4 = rows * (C >> 2);
   long long nb = (n4 + 255) / 256;
   if (nb > 256 * 16) nb = 256 * 16;
-  hipLaunchKernelGGL(bias_act_rows_kernel, dim3((unsigned)nb), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, bias, res, y, n4, C >> 2, relu);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<bias_act_rows_kernel>(
+      dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, bias, res, y, n4, C >> 2, relu);
 }
 
 int pave_fuse_sum_nhwc_f32(const float* s0, int sh0, const float* s1, int sh1, const float* s2, int sh2,
@@ -1930,11 +1878,8 @@ int pave_fuse_sum_nhwc_f32(const float* s0, int sh0, const float* s1, int sh1, c
   const long long n4 = (long long)N * H * W * (C >> 2);
   long long nb = (n4 + 255) / 256;
   if (nb > 256 * 32) nb = 256 * 32;
-  hipLaunchKernelGGL(fuse_sum_kernel, dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     src, y, n4, H, W, C >> 2, relu);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<fuse_sum_kernel>(
+      dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, y, n4, H, W, C >> 2, relu);
 }
 
 int pave_bias_add_layernorm_f32(const float* x, const float* bias, const float* res,
@@ -1958,21 +1903,18 @@ int pave_bias_add_layernorm_pos_f32(const float* x, const float* bias, const flo
   if (nb > 256 * 16) nb = 256 * 16;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int vpl = ((C >> 2) + 63) / 64;
-#define PAVE_LN(V)                                                                              \
-  hipLaunchKernelGGL((bias_add_layernorm_kernel<V>), dim3((unsigned)nb), dim3(256), 0, st, x,   \
-                     bias, res, gamma, beta, y, rows, C, eps, pos, pos_rows, y_plus)
+#define PAVE_LN(V)                                                                                             \
+  return pave_launch<bias_add_layernorm_kernel<V>>(dim3((unsigned)nb), dim3(256), 0, st, x, bias, res, gamma, beta, y, \
+                                                   rows, C, eps, pos, pos_rows, y_plus)
   switch (vpl) {
-    case 1: PAVE_LN(1); break;
-    case 2: PAVE_LN(2); break;
-    case 3: PAVE_LN(3); break;
-    case 4: PAVE_LN(4); break;
-    case 5: case 6: PAVE_LN(6); break;      // (Swin-L: 1536-wide rows; its patch-merging norm: 3072)
-    default: PAVE_LN(12); break;
+    case 1: PAVE_LN(1);
+    case 2: PAVE_LN(2);
+    case 3: PAVE_LN(3);
+    case 4: PAVE_LN(4);
+    case 5: case 6: PAVE_LN(6);      // (Swin-L: 1536-wide rows; its patch-merging norm: 3072)
+    default: PAVE_LN(12);
   }
 #undef PAVE_LN
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
 }
 
 int pave_ms_deform_attn_backward_f32(const float* value, const int64_t* spatial_shapes,
@@ -2010,16 +1952,12 @@ static int preprocess_frames_impl(const void* src, int src_is_u8, float* dst, in
   const float s0 = (float)(1.0 / (double)std[0]), s1 = (float)(1.0 / (double)std[1]),
               s2 = (float)(1.0 / (double)std[2]);
   if (src_is_u8)
-    hipLaunchKernelGGL((preprocess_frames_kernel<unsigned char>), dim3((unsigned)nb), dim3(256), 0,
-                       st, static_cast<const unsigned char*>(src), dst, T, H0, W0, Hn, Wn, Hp, Wp,
-                       mean[0], mean[1], mean[2], s0, s1, s2, to_rgb, flip);
-  else
-    hipLaunchKernelGGL((preprocess_frames_kernel<float>), dim3((unsigned)nb), dim3(256), 0, st,
-                       static_cast<const float*>(src), dst, T, H0, W0, Hn, Wn, Hp, Wp, mean[0],
-                       mean[1], mean[2], s0, s1, s2, to_rgb, flip);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+    return pave_launch<preprocess_frames_kernel<unsigned char>>(
+        dim3((unsigned)nb), dim3(256), 0, st, static_cast<const unsigned char*>(src), dst, T, H0, W0, Hn, Wn, Hp, Wp,
+        mean[0], mean[1], mean[2], s0, s1, s2, to_rgb, flip);
+  return pave_launch<preprocess_frames_kernel<float>>(
+      dim3((unsigned)nb), dim3(256), 0, st, static_cast<const float*>(src), dst, T, H0, W0, Hn, Wn, Hp, Wp, mean[0],
+      mean[1], mean[2], s0, s1, s2, to_rgb, flip);
 }
 
 int pave_preprocess_frames(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
@@ -2047,17 +1985,12 @@ int pave_conv3x3_nhwc_f32(const float* x, const float* w, const float* bias, flo
   const long long gx = ((M + 127) / 128) * (Cout / bn);
   if (gx >= (1ll << 31)) return fail(PAVE_E_ARG, "conv3x3_nhwc: grid too large");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const float* const none = nullptr;
   if (bn == 128)
-    hipLaunchKernelGGL((conv_nhwc_kernel<128, 3>), dim3((unsigned)gx), dim3(256), 0, st, x, w, bias,
-                       (const float*)nullptr, y, N, H, W, Cin, Cout, Ho, Wo, stride, relu,
-                       (const float*)nullptr, (const float*)nullptr, 0);
-  else
-    hipLaunchKernelGGL((conv_nhwc_kernel<64, 3>), dim3((unsigned)gx), dim3(256), 0, st, x, w, bias,
-                       (const float*)nullptr, y, N, H, W, Cin, Cout, Ho, Wo, stride, relu,
-                       (const float*)nullptr, (const float*)nullptr, 0);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+    return pave_launch<conv_nhwc_kernel<128, 3>>(dim3((unsigned)gx), dim3(256), 0, st, x, w, bias, none, y, N, H, W, Cin,
+                                                 Cout, Ho, Wo, stride, relu, none, none, 0);
+  return pave_launch<conv_nhwc_kernel<64, 3>>(dim3((unsigned)gx), dim3(256), 0, st, x, w, bias, none, y, N, H, W, Cin,
+                                              Cout, Ho, Wo, stride, relu, none, none, 0);
 }
 
 int pave_rows_gemm_bias_res_act_f32(const float* a, const float* a_bias, const float* a2,
@@ -2076,14 +2009,10 @@ int pave_rows_gemm_bias_res_act_f32(const float* a, const float* a_bias, const f
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // a 1x1 convolution over a 1 x M "image"
   if (bn == 128)
-    hipLaunchKernelGGL((conv_nhwc_kernel<128, 1>), dim3((unsigned)gx), dim3(256), 0, st, a, w, bias,
-                       residual, out, 1, 1, (int)M, K, Nc, 1, (int)M, 1, relu, a_bias, a2, K2);
-  else
-    hipLaunchKernelGGL((conv_nhwc_kernel<64, 1>), dim3((unsigned)gx), dim3(256), 0, st, a, w, bias,
-                       residual, out, 1, 1, (int)M, K, Nc, 1, (int)M, 1, relu, a_bias, a2, K2);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+    return pave_launch<conv_nhwc_kernel<128, 1>>(dim3((unsigned)gx), dim3(256), 0, st, a, w, bias, residual, out, 1, 1,
+                                                 (int)M, K, Nc, 1, (int)M, 1, relu, a_bias, a2, K2);
+  return pave_launch<conv_nhwc_kernel<64, 1>>(dim3((unsigned)gx), dim3(256), 0, st, a, w, bias, residual, out, 1, 1,
+                                              (int)M, K, Nc, 1, (int)M, 1, relu, a_bias, a2, K2);
 }
 
 int pave_bias_relu_maxpool_nhwc_f32(const float* x, const float* bias, float* y, int N, int H,
@@ -2094,11 +2023,8 @@ int pave_bias_relu_maxpool_nhwc_f32(const float* x, const float* bias, float* y,
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const long long total = (long long)N * Ho * Wo * (C / 4);
   const long long nb = std::min<long long>((total + 255) / 256, 256 * 64);
-  hipLaunchKernelGGL(bias_relu_maxpool_kernel, dim3((unsigned)nb), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, bias, y, N, H, W, C, Ho, Wo);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<bias_relu_maxpool_kernel>(
+      dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, bias, y, N, H, W, C, Ho, Wo);
 }
 
 int pave_groupnorm_nhwc_f32(const float* x, const float* gamma, const float* beta, float* y,
@@ -2114,17 +2040,15 @@ int pave_groupnorm_nhwc_f32(const float* x, const float* gamma, const float* bet
   if (y_batch_stride < (long long)HW * C)
     return fail(PAVE_E_ARG, "groupnorm_nhwc: y_batch_stride smaller than one image");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(groupnorm_stats_kernel, dim3((unsigned)nchunks, (unsigned)N), dim3(256), 0, st,
-                     x, partial, HW, C, G, nchunks);
-  hipLaunchKernelGGL(groupnorm_finalize_kernel, dim3((unsigned)N), dim3(256), 0, st, partial, gamma,
-                     beta, ab, HW, C, G, nchunks, eps);
+  int rc = pave_launch<groupnorm_stats_kernel>(dim3((unsigned)nchunks, (unsigned)N), dim3(256), 0, st, x, partial, HW, C,
+                                               G, nchunks);
+  if (rc != PAVE_OK) return rc;
+  rc = pave_launch<groupnorm_finalize_kernel>(dim3((unsigned)N), dim3(256), 0, st, partial, gamma, beta, ab, HW, C, G,
+                                              nchunks, eps);
+  if (rc != PAVE_OK) return rc;
   const long long total = (long long)N * HW * (C / 4);
   const long long nb = std::min<long long>((total + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(groupnorm_apply_kernel, dim3((unsigned)nb), dim3(256), 0, st, x, ab, y,
-                     y_batch_stride, N, HW, C);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<groupnorm_apply_kernel>(dim3((unsigned)nb), dim3(256), 0, st, x, ab, y, y_batch_stride, N, HW, C);
 }
 
 int pave_groupnorm_levels_nhwc_f32(const pave_gn_level* levels, int nlev, int N, int C, int G, double* partial,
@@ -2159,14 +2083,13 @@ int pave_groupnorm_levels_nhwc_f32(const pave_gn_level* levels, int nlev, int N,
   }
   if (chunks > 65535 * 4ll || blocks >= (1ll << 31)) return fail(PAVE_E_ARG, "groupnorm_levels: grid too large");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(groupnorm_levels_stats_kernel, dim3((unsigned)chunks, (unsigned)N), dim3(256), 0, st, p, partial,
-                     C, G);
-  hipLaunchKernelGGL(groupnorm_levels_finalize_kernel, dim3((unsigned)N, (unsigned)nlev), dim3(256), 0, st, p, partial,
-                     ab, N, C, G);
-  hipLaunchKernelGGL(groupnorm_levels_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, ab, N, C);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  int rc = pave_launch<groupnorm_levels_stats_kernel>(dim3((unsigned)chunks, (unsigned)N), dim3(256), 0, st, p, partial,
+                                                      C, G);
+  if (rc != PAVE_OK) return rc;
+  rc = pave_launch<groupnorm_levels_finalize_kernel>(dim3((unsigned)N, (unsigned)nlev), dim3(256), 0, st, p, partial,
+                                                     ab, N, C, G);
+  if (rc != PAVE_OK) return rc;
+  return pave_launch<groupnorm_levels_apply_kernel>(dim3((unsigned)blocks), dim3(256), 0, st, p, ab, N, C);
 }
 
 int pave_conv3x3s2_c3_nchw_f32(const float* x, const float* w_taps, const float* bias, float* y, int N,
@@ -2176,11 +2099,9 @@ int pave_conv3x3s2_c3_nchw_f32(const float* x, const float* w_taps, const float*
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const long long total = (long long)N * Ho * Wo;
   if ((total + 255) / 256 >= (1ll << 31)) return fail(PAVE_E_ARG, "conv3x3s2_c3: grid too large");
-  hipLaunchKernelGGL(conv3x3s2_c3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, w_taps, bias, y, N, H, W, Ho, Wo, relu);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<conv3x3s2_c3_kernel>(
+      dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, w_taps, bias, y, N,
+      H, W, Ho, Wo, relu);
 }
 
 int pave_ref_update_f32(const float* tmp, const float* ref, float* out, long long n, float eps,
@@ -2188,11 +2109,8 @@ int pave_ref_update_f32(const float* tmp, const float* ref, float* out, long lon
   if (!tmp || !ref || !out) return fail(PAVE_E_ARG, "ref_update: null pointer");
   if (n <= 0) return fail(PAVE_E_ARG, "ref_update: n must be positive");
   const long long nb = std::min<long long>((n + 255) / 256, 1024);
-  hipLaunchKernelGGL(ref_update_kernel, dim3((unsigned)nb), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), tmp, ref, out, n, eps);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PAVE_E_LAUNCH, hipGetErrorString(e));
-  return PAVE_OK;
+  return pave_launch<ref_update_kernel>(
+      dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tmp, ref, out, n, eps);
 }
 
 }  // extern "C"

@@ -136,8 +136,8 @@ _diag_lib = None
 @contextlib.contextmanager
 def diag_build(variant=0):
     """tests/ and tools/ only: inside the block every op of this package runs on the -DPAVE_DIAG
-    build of the same sources with kernel-form override `variant` (pave_gemm_split.hip lists the
-    values); yields that library (it also has pave_diag_enc_tile_ablate).  The shipped library
+    build of the same sources with kernel-form override `variant` (enum PaveDiag in
+    csrc/pave_internal.h lists the values); yields that library (it also has pave_diag_enc_tile_ablate).  The shipped library
     has no such switch, and is back in place when the block ends."""
     global _lib, _diag_lib
     if _diag_lib is None:
