@@ -345,6 +345,21 @@ int pave_preprocess_frames(const void* src, int src_is_u8, float* dst, int T, in
 int pave_preprocess_frames_flip(const void* src, int src_is_u8, float* dst, int T, int H0, int W0,
                                 int Hn, int Wn, int Hp, int Wp, const float* mean, const float* std,
                                 int to_rgb, void* stream);
+/*
+ * The same pipeline fed from NV12 surfaces, as hardware video decoders hand them out (pave_ingest.hip).
+ *   src   T surfaces on the DEVICE, frame_stride bytes apart; a surface is H0 rows of `pitch` bytes of Y, then
+ *         H0 / 2 rows of `pitch` bytes of interleaved U, V.  pitch >= W0; H0 and W0 even.
+ *   csc   HOST float[6] = {yoff, cy, crv, cgu, cgv, cbu}.  Per source pixel, chroma from block (y >> 1, x >> 1):
+ *           t = (Y - yoff) * cy;  B = t + (U - 128) * cbu;  G = (t + (U - 128) * cgu) + (V - 128) * cgv;
+ *           R = t + (V - 128) * crv
+ *         every product and sum rounded to fp32 on its own, then rintf (ties to even) and a clamp to [0, 255].
+ * From that 8-bit BGR value on the arithmetic is pave_preprocess_frames's: dst equals, bit for bit, what
+ * pave_preprocess_frames(src_is_u8 = 1) writes for the converted image.
+ */
+int pave_preprocess_frames_nv12(const void* src, long long frame_stride, int pitch, float* dst,
+                                int T, int H0, int W0, int Hn, int Wn, int Hp, int Wp,
+                                const float* csc, const float* mean, const float* std,
+                                int to_rgb, void* stream);
 
 /*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the

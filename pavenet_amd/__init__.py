@@ -24,3 +24,12 @@ elif 'torch' not in _sys.modules:
     GRAPH_REPLAY_SAFE = True
 else:
     GRAPH_REPLAY_SAFE = False
+
+
+def __getattr__(name):
+    # `from pavenet_amd import LiveVideoPose`: resolved on first use, so that importing the package alone still
+    # does not import torch (the rule above depends on it)
+    if name == 'LiveVideoPose':
+        from .live import LiveVideoPose
+        return LiveVideoPose
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -62,6 +62,54 @@ def preprocess_clip(frames, img_scale=(1333, 800), size_divisor=1, mean=MEAN, st
     return out, meta
 
 
+NV12_MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}   # (Kr, Kb); Kg = 1 - Kr - Kb
+
+
+def nv12_csc(matrix='bt601', full_range=False):
+    """The six coefficients (yoff, cy, crv, cgu, cgv, cbu) of pave_preprocess_frames_nv12 for a Y'CbCr matrix
+    ('bt601' | 'bt709') and range, computed in double: limited range has Y in 16 .. 235 and chroma in 16 .. 240
+    (yoff 16, cy = 255 / 219, chroma factor q = 255 / 224), full range uses all 256 codes (0, 1, 1)."""
+    if matrix not in NV12_MATRICES:
+        raise ValueError(f'nv12_csc: unknown matrix {matrix!r} (one of {sorted(NV12_MATRICES)})')
+    kr, kb = NV12_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    yoff, cy, q = (0.0, 1.0, 1.0) if full_range else (16.0, 255.0 / 219.0, 255.0 / 224.0)
+    return (yoff, cy, 2.0 * (1.0 - kr) * q, -2.0 * kb * (1.0 - kb) * q / kg, -2.0 * kr * (1.0 - kr) * q / kg,
+            2.0 * (1.0 - kb) * q)
+
+
+def preprocess_clip_nv12(surfaces, width, img_scale=(1333, 800), size_divisor=1, mean=MEAN, std=STD,
+                         to_rgb=True, matrix='bt601', full_range=False):
+    """surfaces [T, H0 * 3 // 2, pitch] uint8 NV12 on the device (H0 rows of Y, then H0 / 2 rows of interleaved
+    U, V, `pitch` bytes each, of which the first `width` belong to the picture) -> the same (img [1, T, 3, Hp, Wp]
+    fp32, img_meta) as preprocess_clip gives for the H0 x width BGR picture the conversion of nv12_csc(matrix,
+    full_range) produces, in one launch and without that picture ever being stored."""
+    if not (isinstance(surfaces, torch.Tensor) and surfaces.dim() == 3 and surfaces.dtype == torch.uint8):
+        raise ValueError('preprocess_clip_nv12: surfaces must be a [T, H0 * 3 // 2, pitch] uint8 tensor')
+    T, rows, pitch = surfaces.shape
+    H0, W0 = rows * 2 // 3, int(width)
+    if rows % 3 != 0 or H0 % 2 != 0 or H0 <= 0:
+        raise ValueError(f'preprocess_clip_nv12: {rows} rows are not the 3/2 of an even height')
+    if W0 <= 0 or W0 % 2 != 0:
+        raise ValueError(f'preprocess_clip_nv12: width {W0} must be even and positive')
+    if W0 > pitch:
+        raise ValueError(f'preprocess_clip_nv12: width {W0} exceeds the pitch {pitch}')
+    csc = (ctypes.c_float * 6)(*nv12_csc(matrix, full_range))
+    _require(surfaces.is_cuda and surfaces.is_contiguous() and T > 0,
+             'preprocess_clip_nv12: surfaces must be a contiguous device tensor')
+    Hn, Wn, Hp, Wp, scale_factor = plan_clip(H0, W0, img_scale, size_divisor)
+    out = torch.empty((1, T, 3, Hp, Wp), dtype=torch.float32, device=surfaces.device)
+    m = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    _launch('pave_preprocess_frames_nv12', 'preprocess_frames_nv12', surfaces.device,
+            surfaces.data_ptr(), rows * pitch, pitch, out.data_ptr(), T, H0, W0, Hn, Wn, Hp, Wp,
+            ctypes.cast(csc, ctypes.c_void_p), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
+            int(bool(to_rgb)))
+    meta = dict(ori_shape=(H0, W0, 3), img_shape=(Hn, Wn, 3), pad_shape=(Hp, Wp, 3),
+                batch_input_shape=(Hp, Wp), scale_factor=scale_factor, flip=False, flip_direction=None)
+    return out, meta
+
+
 def aug_plan(img_scale, flip=False, flip_direction='horizontal'):
     """mmdet MultiScaleFlipAug's order (mmdet/datasets/pipelines/test_time_aug.py:54-110): scales outer, flips
     inner, [(False, None)] + [(True, d) for d in flip_direction] -> [(scale, flip, direction), ...]."""

@@ -21,6 +21,9 @@ The projected values belong to the slab list ``encode`` returns (``FrameSlabs.va
 uses the frame table only with such a list whose cache covers every slab in it, so slabs kept from
 an earlier ``encode``, of another video, or a plain list take the per-window projection instead of
 indexing somebody else's cache.  ``encode(frames, into=slabs)`` appends to both.
+
+``infer_video`` keeps all of that for every frame of the video; ``live.LiveVideoPose`` (and ``infer_frames`` through
+it) is the frame-by-frame form on a ring of T - 1 + max_push reused slots, for camera feeds and long videos.
 """
 import torch
 
@@ -39,6 +42,10 @@ class FrameSlabs(list):
         self.n_cached = 0        # frames whose projected values are in `values`
         self.geom = None
         self.levels = None
+
+    def _append_memory(self, memory):
+        """Encoder memory [n, S, C] of the frames a chunk of `_encode` has just encoded."""
+        self.extend(memory.unbind(0))
 
     def _append_values(self, vals, n_pose, expected_total):
         """Projected values of the frames just appended (one tensor [n, ...] per decoder layer)."""
@@ -103,7 +110,7 @@ class VideoPoseStream:
             memory, _, _, geom = self.tr.encode_frames(feats, masks, pos, has_padding)
             slabs.geom, slabs.levels = geom, [tuple(f.shape[-2:]) for f in feats]
             self._last_levels = slabs.levels
-            slabs.extend(memory.unbind(0))
+            slabs._append_memory(memory)
             if caching and not has_padding and memory.is_cuda:
                 # value_proj of every decoder layer, once per frame (padded batches mask the value
                 # per window and keep the per-window projection)
@@ -175,3 +182,17 @@ class VideoPoseStream:
                 res = self.decode(slabs, wins[i:i + self.decode_chunk], rescale=rescale)
                 results.extend(self.head.results_to_list(res))
             return results
+
+    def infer_frames(self, chunks, rescale=False):
+        """The long-video form of `infer_video`: `chunks` is an iterable of [n, 3, H, W] (or [3, H, W]) device
+        tensors in frame order; yields (frame index, (bboxes, labels, kpts)) as each frame's window becomes
+        decidable and the last T // 2 when the iterable ends.  The frames go through a `live.LiveVideoPose` ring of
+        T - 1 + encode_chunk slots, so the resident memory does not depend on the video's length."""
+        from .live import LiveVideoPose
+        live = LiveVideoPose(self.model, self.meta, max_push=self.encode_chunk, decode_chunk=self.decode_chunk,
+                             rescale=rescale, cache_values=self.cache_values)
+        for chunk in chunks:
+            chunk = chunk[None] if chunk.dim() == 3 else chunk
+            for i in range(0, chunk.shape[0], self.encode_chunk):
+                yield from live.push(chunk[i:i + self.encode_chunk])
+        yield from live.flush()
