@@ -360,6 +360,44 @@ int pave_preprocess_frames_nv12(const void* src, long long frame_stride, int pit
                                 int T, int H0, int W0, int Hn, int Wn, int Hp, int Wp,
                                 const float* csc, const float* mean, const float* std,
                                 int to_rgb, void* stream);
+/*
+ * The same for n separately allocated surfaces in one launch (several cameras: each decoder hands out its own
+ * allocation, pitch, matrix and range).  The plan is copied into the kernel's arguments (no host->device copy).
+ *   src[i], pitch[i], csc[i]  surface i as above (one surface, no frame_stride); H0 x W0 is the same for all
+ *   dst   [n, 3, Hp, Wp]: dst[i] equals, bit for bit, what pave_preprocess_frames_nv12 writes for surface i alone
+ *         with csc[i] (both kernels run one per-pixel function)
+ * 1 <= n <= PAVE_INGEST_MAX_SURFACES, every src[i] non-null, every pitch[i] >= W0; H0 and W0 even.
+ */
+#define PAVE_INGEST_MAX_SURFACES 32
+typedef struct pave_ingest_plan {
+  const void* src[PAVE_INGEST_MAX_SURFACES];    /* DEVICE: H0 rows of pitch[i] bytes of Y, then H0 / 2 rows of UV */
+  int         pitch[PAVE_INGEST_MAX_SURFACES];
+  float       csc[PAVE_INGEST_MAX_SURFACES][6]; /* yoff, cy, crv, cgu, cgv, cbu as in pave_preprocess_frames_nv12 */
+  int n;
+} pave_ingest_plan;
+int pave_preprocess_surfaces_nv12(const pave_ingest_plan* plan, float* dst, int H0, int W0, int Hn, int Wn, int Hp,
+                                  int Wp, const float* mean, const float* std, int to_rgb, void* stream);
+
+/*
+ * Row scatter of the live ring (pavenet_amd/live.py CameraRing): dst[t][row[i]] = src[t][i] for i < n and the first
+ * k tensors, a plain copy in one launch.  The plan is a HOST struct copied into the kernel's arguments.
+ *   src[t]  DEVICE [n, row_elems] fp32, dense;  dst[t]  DEVICE [dst_rows, row_elems] fp32, dense
+ *   row[i]  the destination row of source row i
+ * Refused with PAVE_E_ARG before any device call: a null pointer among the first k, n outside 1 .. 64, k outside
+ * 1 .. 8, dst_rows or row_elems < 1, row_elems not a multiple of 4, a pointer that is not 16-byte aligned (the
+ * kernel moves 16 bytes per lane), a row[i] outside [0, dst_rows), two equal row[i] (the result would depend on
+ * block order).  A plan that passes cannot address memory outside its tensors.
+ */
+#define PAVE_SCATTER_MAX_ROWS 64
+#define PAVE_SCATTER_MAX_TENSORS 8
+typedef struct pave_scatter_plan {
+  const void* src[PAVE_SCATTER_MAX_TENSORS];
+  void*       dst[PAVE_SCATTER_MAX_TENSORS];
+  int         row[PAVE_SCATTER_MAX_ROWS];
+  int n, k, dst_rows;
+  long long row_elems;
+} pave_scatter_plan;
+int pave_scatter_rows_f32(const pave_scatter_plan* plan, void* stream);
 
 /*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the

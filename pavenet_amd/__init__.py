@@ -29,7 +29,7 @@ else:
 def __getattr__(name):
     # `from pavenet_amd import LiveVideoPose`: resolved on first use, so that importing the package alone still
     # does not import torch (the rule above depends on it)
-    if name == 'LiveVideoPose':
-        from .live import LiveVideoPose
-        return LiveVideoPose
+    if name in ('LiveVideoPose', 'MultiLiveVideoPose', 'CameraRing'):
+        from . import live
+        return getattr(live, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -94,6 +94,23 @@ class AugPlan(ctypes.Structure):
                 ('N', ctypes.c_int32), ('K', ctypes.c_int32)]
 
 
+INGEST_MAX_SURFACES = DEFINES['PAVE_INGEST_MAX_SURFACES']
+SCATTER_MAX_ROWS, SCATTER_MAX_TENSORS = DEFINES['PAVE_SCATTER_MAX_ROWS'], DEFINES['PAVE_SCATTER_MAX_TENSORS']
+
+
+class IngestPlan(ctypes.Structure):
+    """`pave_ingest_plan` of include/pave_hip.h (the by-value argument of pave_preprocess_surfaces_nv12)."""
+    _fields_ = [('src', ctypes.c_void_p * INGEST_MAX_SURFACES), ('pitch', ctypes.c_int * INGEST_MAX_SURFACES),
+                ('csc', (ctypes.c_float * 6) * INGEST_MAX_SURFACES), ('n', ctypes.c_int)]
+
+
+class ScatterPlan(ctypes.Structure):
+    """`pave_scatter_plan` of include/pave_hip.h (the by-value argument of pave_scatter_rows_f32)."""
+    _fields_ = [('src', ctypes.c_void_p * SCATTER_MAX_TENSORS), ('dst', ctypes.c_void_p * SCATTER_MAX_TENSORS),
+                ('row', ctypes.c_int * SCATTER_MAX_ROWS), ('n', ctypes.c_int), ('k', ctypes.c_int),
+                ('dst_rows', ctypes.c_int), ('row_elems', ctypes.c_longlong)]
+
+
 _lib = None
 
 

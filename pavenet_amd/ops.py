@@ -489,6 +489,47 @@ def hflip_canvas(x, valid_w):
     return y
 
 
+def scatter_rows(srcs, dsts, rows):
+    """dsts[t][rows[i]] = srcs[t][i] for every tensor pair t and source row i, in one launch per 64 rows
+    (pave_scatter_rows_f32; the live ring's write).  srcs[t] [n, ...] and dsts[t] [dst_rows, ...] are contiguous fp32
+    device tensors, all with the same number of elements per row (a multiple of 4) and 16-byte aligned; `rows` are n
+    distinct ints in [0, dst_rows).  A plain copy: bit-identical to the indexed assignment."""
+    K, N = native.SCATTER_MAX_TENSORS, native.SCATTER_MAX_ROWS
+    srcs, dsts, rows = list(srcs), list(dsts), [int(r) for r in rows]
+    if not 0 < len(srcs) <= K or len(dsts) != len(srcs):
+        raise ValueError(f'scatter_rows: 1 .. {K} (src, dst) tensor pairs, got {len(srcs)} and {len(dsts)}')
+    if not all(isinstance(x, torch.Tensor) and x.dim() >= 2 and x.dtype == torch.float32 for x in srcs + dsts):
+        raise ValueError('scatter_rows: srcs and dsts are fp32 tensors of [rows, ...]')
+    n, dst_rows, row_elems = len(rows), dsts[0].shape[0], srcs[0][0].numel() if srcs[0].shape[0] else 0
+    if n == 0 or len(set(rows)) != n:
+        raise ValueError('scatter_rows: `rows` are 1 or more distinct destination rows')
+    if min(rows) < 0 or max(rows) >= dst_rows:
+        raise ValueError(f'scatter_rows: rows must lie in [0, {dst_rows})')
+    if row_elems < 4 or row_elems % 4 != 0:
+        raise ValueError(f'scatter_rows: {row_elems} elements per row, a positive multiple of 4 is needed')
+    for t, (s, d) in enumerate(zip(srcs, dsts)):
+        for x, name, lead in ((s, f'srcs[{t}]', n), (d, f'dsts[{t}]', dst_rows)):
+            if x.shape[0] != lead or x.numel() != lead * row_elems:
+                raise ValueError(f'scatter_rows: {name} must hold {lead} rows of {row_elems} elements, '
+                                 f'got {tuple(x.shape)}')
+            if x.data_ptr() % 16 != 0:
+                raise ValueError(f'scatter_rows: {name} is not 16-byte aligned')
+    dev = dsts[0].device
+    for t, x in enumerate(srcs + dsts):
+        _dev(x, f'tensor {t}', torch.float32)
+        _require(x.device == dev, 'scatter_rows: all tensors on one device')
+    for at in range(0, n, N):
+        part = rows[at:at + N]
+        plan = native.ScatterPlan()
+        for t, (s, d) in enumerate(zip(srcs, dsts)):
+            plan.src[t] = s.data_ptr() + at * row_elems * 4
+            plan.dst[t] = d.data_ptr()
+        for i, r in enumerate(part):
+            plan.row[i] = r
+        plan.n, plan.k, plan.dst_rows, plan.row_elems = len(part), len(srcs), dst_rows, row_elems
+        _launch('pave_scatter_rows_f32', 'scatter_rows', dev, ctypes.byref(plan))
+
+
 def fuse_sum_nhwc(terms, relu=True):
     """HRNet fuse layer in one pass (pave_fuse_sum_nhwc_f32): terms = [(map, shift), ...] (1..4), map
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones

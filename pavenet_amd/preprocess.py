@@ -12,6 +12,7 @@ import ctypes
 
 import torch
 
+from . import native
 from .ops import _launch, _require
 
 MEAN = (123.675, 116.28, 103.53)
@@ -105,6 +106,66 @@ def preprocess_clip_nv12(surfaces, width, img_scale=(1333, 800), size_divisor=1,
             surfaces.data_ptr(), rows * pitch, pitch, out.data_ptr(), T, H0, W0, Hn, Wn, Hp, Wp,
             ctypes.cast(csc, ctypes.c_void_p), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
             int(bool(to_rgb)))
+    meta = dict(ori_shape=(H0, W0, 3), img_shape=(Hn, Wn, 3), pad_shape=(Hp, Wp, 3),
+                batch_input_shape=(Hp, Wp), scale_factor=scale_factor, flip=False, flip_direction=None)
+    return out, meta
+
+
+def preprocess_surfaces_nv12(surfaces, width, img_scale=(1333, 800), size_divisor=1, mean=MEAN, std=STD,
+                             to_rgb=True, matrix='bt601', full_range=False):
+    """surfaces: a list of n separately allocated [H0 * 3 // 2, pitch_i] uint8 NV12 device tensors of one H0 x width
+    picture size (several cameras: each with its own pitch); `matrix` and `full_range` one value or one per
+    surface -> (img [n, 3, Hp, Wp] fp32, img_meta): img[i] equals preprocess_clip_nv12(surfaces[i][None], ...)
+    with surface i's settings bit for bit, the meta is that call's.  One launch per 32 surfaces
+    (pave_preprocess_surfaces_nv12)."""
+    surfaces = list(surfaces) if isinstance(surfaces, (list, tuple)) else None
+    if not surfaces:
+        raise ValueError('preprocess_surfaces_nv12: surfaces must be a non-empty list of [H0 * 3 // 2, pitch] tensors')
+    n, W0 = len(surfaces), int(width)
+    for i, s in enumerate(surfaces):
+        if not (isinstance(s, torch.Tensor) and s.dim() == 2 and s.dtype == torch.uint8):
+            raise ValueError(f'preprocess_surfaces_nv12: surfaces[{i}] must be a [H0 * 3 // 2, pitch] uint8 tensor')
+    rows = surfaces[0].shape[0]
+    H0 = rows * 2 // 3
+    if rows % 3 != 0 or H0 % 2 != 0 or H0 <= 0:
+        raise ValueError(f'preprocess_surfaces_nv12: {rows} rows are not the 3/2 of an even height')
+    if W0 <= 0 or W0 % 2 != 0:
+        raise ValueError(f'preprocess_surfaces_nv12: width {W0} must be even and positive')
+    for i, s in enumerate(surfaces):
+        if s.shape[0] != rows:
+            raise ValueError(f'preprocess_surfaces_nv12: surfaces[{i}] has {s.shape[0]} rows, surfaces[0] {rows} '
+                             '(one launch takes one source size)')
+        if W0 > s.shape[1]:
+            raise ValueError(f'preprocess_surfaces_nv12: width {W0} exceeds the pitch {s.shape[1]} of surfaces[{i}]')
+
+    def per_surface(v, name, scalar):
+        if isinstance(v, scalar):
+            return [v] * n
+        v = list(v)
+        if len(v) != n:
+            raise ValueError(f'preprocess_surfaces_nv12: {name} is one value or one per surface ({n}), got {len(v)}')
+        return v
+    cscs = [nv12_csc(m, bool(f)) for m, f in zip(per_surface(matrix, 'matrix', str),
+                                                 per_surface(full_range, 'full_range', (bool, int)))]
+    dev = surfaces[0].device
+    _require(all(s.is_cuda and s.is_contiguous() and s.device == dev for s in surfaces),
+             'preprocess_surfaces_nv12: surfaces must be contiguous tensors on one device')
+    Hn, Wn, Hp, Wp, scale_factor = plan_clip(H0, W0, img_scale, size_divisor)
+    out = torch.empty((n, 3, Hp, Wp), dtype=torch.float32, device=dev)
+    m = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    for at in range(0, n, native.INGEST_MAX_SURFACES):
+        plan = native.IngestPlan()
+        part = surfaces[at:at + native.INGEST_MAX_SURFACES]
+        for i, surf in enumerate(part):
+            plan.src[i] = surf.data_ptr()
+            plan.pitch[i] = surf.shape[1]
+            for j, c in enumerate(cscs[at + i]):
+                plan.csc[i][j] = c
+        plan.n = len(part)
+        _launch('pave_preprocess_surfaces_nv12', 'preprocess_surfaces_nv12', dev, ctypes.byref(plan),
+                out[at:].data_ptr(), H0, W0, Hn, Wn, Hp, Wp, ctypes.cast(m, ctypes.c_void_p),
+                ctypes.cast(s, ctypes.c_void_p), int(bool(to_rgb)))
     meta = dict(ori_shape=(H0, W0, 3), img_shape=(Hn, Wn, 3), pad_shape=(Hp, Wp, 3),
                 batch_input_shape=(Hp, Wp), scale_factor=scale_factor, flip=False, flip_direction=None)
     return out, meta
