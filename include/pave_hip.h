@@ -400,6 +400,56 @@ typedef struct pave_scatter_plan {
 int pave_scatter_rows_f32(const pave_scatter_plan* plan, void* stream);
 
 /*
+ * Poses drawn into surfaces on the device (pavenet_amd/csrc/pave_draw.hip; the rule is DESIGN section 13), one launch
+ * for n separately allocated surfaces of any sizes.  The plan is copied into the kernel's arguments.
+ *   dst[i]     DEVICE, written in place.  _nv12: height[i] rows of pitch[i] bytes of Y, then height[i] / 2 rows of
+ *              interleaved U, V (width and height even, pitch >= width).  _bgr: [height, width, 3] bytes, pitch[i]
+ *              bytes per row (>= 3 width)
+ *   kpts[i]    DEVICE [n_poses[i], K, 3] fp32 (x, y, score);  bboxes[i] [n_poses[i], 5] fp32 (x1, y1, x2, y2, score);
+ *              keep[i] [n_poses[i]] int32 or NULL.  Both may be NULL where n_poses[i] == 0
+ *   scale[i]   (sx, sy): a coordinate x becomes clamp((int)rintf((x / sx) * 4.f), 0, 32767) quarter pixels
+ *   table[i]   which of the 4 colour tables surface i takes (NV12: one per matrix and range)
+ *   color[t]   row 0: boxes; rows 1 .. 32: limbs; rows 33 .. 64: key points; 3 bytes each, stored as they are --
+ *              (Y, U, V) for _nv12, (B, G, R) for _bgr
+ *   edge[e]    limb e joins key points edge[e][0] and edge[e][1]
+ * Pose p is drawn iff keep[p] != 0 (keep given), bboxes[p][4] > score_thr and its 2 K + 4 coordinates are finite;
+ * key point k is visible iff its score > kpt_thr; a limb needs both ends.  Primitives of pose p in local order: 4 box
+ * edges (draw_boxes != 0), E limbs (radius 2 thickness quarter pixels), K discs (radius 4 radius); a pixel takes the
+ * colour of the covering primitive with the largest id p (4 + E + K) + local, an NV12 chroma sample the largest over
+ * its 2 x 2 luma pixels.  No byte that nothing covers is written.
+ * Refused with PAVE_E_ARG before any device call: a null plan, surface or pose tensor (n_poses > 0), n outside
+ * 1 .. 32, width or height outside 1 .. 8192, odd NV12 sizes, a pitch below a row's bytes, n_poses outside 0 .. 4096,
+ * K outside 1 .. 32, E outside 0 .. 32, an edge index >= K, thickness outside 1 .. 32, radius outside 0 .. 32, a scale
+ * that is not positive and finite, a table index >= 4.  A plan that passes cannot address memory outside its
+ * tensors, whatever the pose values are.
+ */
+#define PAVE_DRAW_MAX_SURFACES 32
+#define PAVE_DRAW_MAX_K 32
+#define PAVE_DRAW_MAX_E 32
+#define PAVE_DRAW_MAX_TABLES 4
+#define PAVE_DRAW_COLORS 65
+#define PAVE_DRAW_MAX_POSES 4096
+#define PAVE_DRAW_MAX_SIZE 8192
+typedef struct pave_draw_plan {
+  void*          dst[PAVE_DRAW_MAX_SURFACES];
+  const float*   kpts[PAVE_DRAW_MAX_SURFACES];
+  const float*   bboxes[PAVE_DRAW_MAX_SURFACES];
+  const int32_t* keep[PAVE_DRAW_MAX_SURFACES];
+  int            pitch[PAVE_DRAW_MAX_SURFACES];
+  int            width[PAVE_DRAW_MAX_SURFACES];
+  int            height[PAVE_DRAW_MAX_SURFACES];
+  int            n_poses[PAVE_DRAW_MAX_SURFACES];
+  float          scale[PAVE_DRAW_MAX_SURFACES][2];
+  uint8_t        table[PAVE_DRAW_MAX_SURFACES];
+  uint8_t        color[PAVE_DRAW_MAX_TABLES][PAVE_DRAW_COLORS][3];
+  uint8_t        edge[PAVE_DRAW_MAX_E][2];
+  int n, K, E, thickness, radius, draw_boxes;
+  float score_thr, kpt_thr;
+} pave_draw_plan;
+int pave_draw_poses_nv12(const pave_draw_plan* plan, void* stream);
+int pave_draw_poses_bgr(const pave_draw_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

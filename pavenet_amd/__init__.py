@@ -32,4 +32,7 @@ def __getattr__(name):
     if name in ('LiveVideoPose', 'MultiLiveVideoPose', 'CameraRing'):
         from . import live
         return getattr(live, name)
+    if name in ('PoseStyle', 'draw_poses_nv12', 'draw_poses_bgr', 'bgr_to_yuv'):
+        from . import render
+        return getattr(render, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

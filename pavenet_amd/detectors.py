@@ -180,6 +180,17 @@ class VideoPoseV1(BaseModule):
         results_list = self.bbox_head.results_to_list(res)
         return [bbox_kpt2result(b, l, k, self.bbox_head.num_classes) for b, l, k in results_list]
 
+    def show_result(self, img, result, score_thr=0.3, bbox_color=(72, 101, 241), text_color=(72, 101, 241),
+                    mask_color=None, thickness=4, font_size=10, win_name='', show=False, wait_time=0, out_file=None,
+                    **style):
+        """videoposev1.py:263-350 / petr.py:189 on the device (``render.show_result``): a drawn copy of the [H, W, 3]
+        uint8 BGR `img` with the poses and boxes of `result` (one image's entry of ``simple_test``), hard-edged and
+        without text; show=True / out_file= raise NotImplementedError.  **style: radius, kpt_thr, skeleton."""
+        from .render import show_result
+        return show_result(self, img, result, score_thr=score_thr, bbox_color=bbox_color, text_color=text_color,
+                           mask_color=mask_color, thickness=thickness, font_size=font_size, win_name=win_name,
+                           show=show, wait_time=wait_time, out_file=out_file, **style)
+
     def forward(self, img, img_metas, return_loss=False, rescale=False, **kwargs):
         if return_loss:
             raise NotImplementedError('pavenet_amd is a forward (inference) path')

@@ -111,6 +111,24 @@ class ScatterPlan(ctypes.Structure):
                 ('dst_rows', ctypes.c_int), ('row_elems', ctypes.c_longlong)]
 
 
+DRAW_MAX_SURFACES, DRAW_MAX_K, DRAW_MAX_E, DRAW_MAX_TABLES, DRAW_COLORS, DRAW_MAX_POSES, DRAW_MAX_SIZE = (
+    DEFINES['PAVE_DRAW_' + n] for n in ('MAX_SURFACES', 'MAX_K', 'MAX_E', 'MAX_TABLES', 'COLORS', 'MAX_POSES',
+                                        'MAX_SIZE'))
+
+
+class DrawPlan(ctypes.Structure):
+    """`pave_draw_plan` of include/pave_hip.h (the by-value argument of pave_draw_poses_nv12 / _bgr)."""
+    _fields_ = [('dst', ctypes.c_void_p * DRAW_MAX_SURFACES), ('kpts', ctypes.c_void_p * DRAW_MAX_SURFACES),
+                ('bboxes', ctypes.c_void_p * DRAW_MAX_SURFACES), ('keep', ctypes.c_void_p * DRAW_MAX_SURFACES),
+                ('pitch', ctypes.c_int * DRAW_MAX_SURFACES), ('width', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('height', ctypes.c_int * DRAW_MAX_SURFACES), ('n_poses', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('scale', (ctypes.c_float * 2) * DRAW_MAX_SURFACES), ('table', ctypes.c_uint8 * DRAW_MAX_SURFACES),
+                ('color', ((ctypes.c_uint8 * 3) * DRAW_COLORS) * DRAW_MAX_TABLES),
+                ('edge', (ctypes.c_uint8 * 2) * DRAW_MAX_E), ('n', ctypes.c_int), ('K', ctypes.c_int),
+                ('E', ctypes.c_int), ('thickness', ctypes.c_int), ('radius', ctypes.c_int),
+                ('draw_boxes', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
+
+
 _lib = None
 
 

@@ -530,6 +530,96 @@ def scatter_rows(srcs, dsts, rows):
         _launch('pave_scatter_rows_f32', 'scatter_rows', dev, ctypes.byref(plan))
 
 
+def draw_poses(kind, items, colors, edges, K, *, thickness=4, radius=4, score_thr=0.3, kpt_thr=0., draw_boxes=False):
+    """Poses drawn into surfaces in place, one launch per 32 surfaces (pave_draw_poses_nv12 / _bgr; the rule is
+    DESIGN section 13).  kind 'nv12': a surface is a [H * 3 // 2, pitch] uint8 tensor whose first `width` columns are
+    the picture; 'bgr': a [H, W, 3] uint8 tensor (`width` is not read).  items: one (surface, width, kpts [N, K, 3]
+    fp32, bboxes [N, 5] fp32, keep [N] int32 or None, (sx, sy), table) per surface; colors [tables <= 4, 65, 3] bytes
+    stored as they are (row 0 boxes, 1 .. 32 limbs, 33 .. 64 key points; a table nested or as its 195 bytes); edges: E <= 32 pairs of key-point indices.
+    Shapes, types and ranges raise ValueError before anything is asked of a device."""
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"draw_poses: kind {kind!r} is not 'nv12' or 'bgr'")
+    items, edges, K = list(items), [(int(a), int(b)) for a, b in edges], int(K)
+    if not 1 <= K <= native.DRAW_MAX_K or len(edges) > native.DRAW_MAX_E:
+        raise ValueError(f'draw_poses: K in 1 .. {native.DRAW_MAX_K} and at most {native.DRAW_MAX_E} edges, got K = {K} '
+                         f'and {len(edges)} edges')
+    if any(not (0 <= a < K and 0 <= b < K) for a, b in edges):
+        raise ValueError(f'draw_poses: an edge index outside [0, {K})')
+    if not 1 <= int(thickness) <= 32 or not 0 <= int(radius) <= 32:
+        raise ValueError(f'draw_poses: thickness in 1 .. 32 and radius in 0 .. 32, got {thickness} and {radius}')
+    try:   # (a table may come as the 195 bytes themselves: PoseStyle caches them)
+        colors = [tab if isinstance(tab, bytes) else bytes(int(c) for row in tab for c in (row if len(row) == 3 else ()))
+                  for tab in colors]
+    except (TypeError, ValueError):
+        colors = []
+    if not 1 <= len(colors) <= native.DRAW_MAX_TABLES or any(len(tab) != 3 * native.DRAW_COLORS for tab in colors):
+        raise ValueError(f'draw_poses: colors are 1 .. {native.DRAW_MAX_TABLES} tables of {native.DRAW_COLORS} x 3 bytes')
+    if not items:
+        raise ValueError('draw_poses: no surface')
+    geometry = []
+    for i, (surf, width, kpts, bboxes, keep, scale, table) in enumerate(items):
+        if not (isinstance(surf, torch.Tensor) and surf.dtype == torch.uint8):
+            raise ValueError(f'draw_poses: surface {i} must be a uint8 tensor')
+        if kind == 'nv12':
+            if surf.dim() != 2:
+                raise ValueError(f'draw_poses: surface {i} must be [H * 3 // 2, pitch], got {tuple(surf.shape)}')
+            rows, pitch = surf.shape
+            H, W, row_bytes = rows * 2 // 3, int(width), int(width)
+            if rows % 3 != 0 or H % 2 != 0 or H <= 0:
+                raise ValueError(f'draw_poses: surface {i}: {rows} rows are not the 3/2 of an even height')
+            if W <= 0 or W % 2 != 0:
+                raise ValueError(f'draw_poses: surface {i}: width {W} must be even and positive')
+        else:
+            if surf.dim() != 3 or surf.shape[2] != 3 or surf.shape[0] < 1 or surf.shape[1] < 1:
+                raise ValueError(f'draw_poses: surface {i} must be [H, W, 3], got {tuple(surf.shape)}')
+            H, W = surf.shape[:2]
+            pitch = row_bytes = 3 * W
+        if row_bytes > pitch:
+            raise ValueError(f'draw_poses: surface {i}: width {W} exceeds the pitch {pitch}')
+        if W > native.DRAW_MAX_SIZE or H > native.DRAW_MAX_SIZE:
+            raise ValueError(f'draw_poses: surface {i}: {W} x {H} exceeds {native.DRAW_MAX_SIZE} x {native.DRAW_MAX_SIZE}')
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'draw_poses: kpts of surface {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'draw_poses: bboxes of surface {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'draw_poses: keep of surface {i} must be a [{N}] int32 tensor')
+        if N > native.DRAW_MAX_POSES:
+            raise ValueError(f'draw_poses: surface {i} has {N} poses, at most {native.DRAW_MAX_POSES}')
+        sx, sy = (float(v) for v in scale)
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'draw_poses: the scale of surface {i} must be positive and finite, got {(sx, sy)}')
+        if not 0 <= int(table) < len(colors):
+            raise ValueError(f'draw_poses: surface {i} names colour table {table} of {len(colors)}')
+        geometry.append((int(pitch), int(W), int(H), N, sx, sy, int(table)))
+    dev = items[0][0].device
+    for i, (surf, _, kpts, bboxes, keep, _, _) in enumerate(items):
+        for t, name in ((surf, 'surface'), (kpts, 'kpts'), (bboxes, 'bboxes'), (keep, 'keep')):
+            if t is not None:
+                _dev(t, f'draw_poses: {name} of surface {i}')
+                _require(t.device == dev, 'draw_poses: all tensors on one device')
+    entry = 'pave_draw_poses_nv12' if kind == 'nv12' else 'pave_draw_poses_bgr'
+    raw_colors = b''.join(colors)   # [tables][65][3], the plan's layout
+    for at in range(0, len(items), native.DRAW_MAX_SURFACES):
+        plan = native.DrawPlan()
+        part = items[at:at + native.DRAW_MAX_SURFACES]
+        for i, (surf, _, kpts, bboxes, keep, _, _) in enumerate(part):
+            pitch, W, H, N, sx, sy, table = geometry[at + i]
+            plan.dst[i], plan.kpts[i], plan.bboxes[i], plan.keep[i] = surf.data_ptr(), kpts.data_ptr(), \
+                bboxes.data_ptr(), _ptr(keep)
+            plan.pitch[i], plan.width[i], plan.height[i], plan.n_poses[i] = pitch, W, H, N
+            plan.scale[i][0], plan.scale[i][1], plan.table[i] = sx, sy, table
+        ctypes.memmove(plan.color, raw_colors, len(raw_colors))
+        for e, (a, b) in enumerate(edges):
+            plan.edge[e][0], plan.edge[e][1] = a, b
+        plan.n, plan.K, plan.E, plan.thickness, plan.radius = len(part), K, len(edges), int(thickness), int(radius)
+        plan.draw_boxes, plan.score_thr, plan.kpt_thr = int(bool(draw_boxes)), float(score_thr), float(kpt_thr)
+        _launch(entry, 'draw_poses', dev, ctypes.byref(plan))
+
+
 def fuse_sum_nhwc(terms, relu=True):
     """HRNet fuse layer in one pass (pave_fuse_sum_nhwc_f32): terms = [(map, shift), ...] (1..4), map
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones
