@@ -170,7 +170,10 @@ int pave_mha_core_f32(const float* qkv, float* out, int n_seq, int L, int H, int
 /*
  * Row-wise top-k in one launch: element (r, i) of x at x[r ld + i cs], i < n; k <= 1024,
  * n <= 32768 -> index [rows, k] int64 sorted by (value descending, index ascending), values
- * [rows, k] (may be NULL).  NaN ranks above +inf (torch.topk's order).  Replaces torch.topk for the
+ * [rows, k] (may be NULL).  A NaN of either sign ranks above +inf (torch.topk's order), NaNs among
+ * themselves by ascending index.  -0.0 and +0.0 are equal values: between them the lower index comes
+ * first, also in the selection at the k-th value.  The values are read back from x, so they keep the
+ * input's sign bits.  Replaces torch.topk for the
  * proposal selection (opera/models/utils/transformer.py:21383-21385) and the score selection
  * (opera/models/dense_heads/videopose_head_mul_frames.py:1416).
  */
@@ -232,6 +235,8 @@ int pave_proposal_refs_f32(float* kpt, int ld, const float* props, long long pro
  *   kpts   [n_clips, N, K, 3] (x, y, score) pixels;  scores [n_clips, N];  sigmas [K] double, DEVICE
  *   keep   [n_clips, N] int32: 1 = kept;  order [n_clips, N] int32: indices by descending score
  * A pose is suppressed when its OKS with an earlier kept pose is > thresh.
+ * Equal scores come out larger index first (the reverse of a stable ascending sort), and a NaN
+ * score sorts as +inf, so `order` is a permutation of 0 .. N - 1 for any input.  N <= 4096.
  */
 int pave_oks_nms_f32(const float* kpts, const float* scores, const double* sigmas, double thresh,
                      int32_t* keep, int32_t* order, int n_clips, int N, int K, void* stream);

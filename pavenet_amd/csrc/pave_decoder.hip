@@ -221,7 +221,10 @@ extern "C" int pave_mha_core_f32(const float* qkv, float* out, int n_seq, int L,
 // LDS once (coalesced), the k-th largest value is found by a 4 x 8-bit radix select over
 // order-preserving keys, the k winners are compacted in index order (ties at the k-th value: the
 // lowest indices, whatever the launch geometry) and sorted by (value descending, index
-// ascending) with a bitonic network in LDS.  NaN ranks above +inf, as in torch.topk.
+// ascending) with a bitonic network in LDS.  A NaN of either sign ranks above +inf, as in torch.topk
+// (NaNs among themselves: index ascending); -0.0 and +0.0 are equal values, so between them the
+// lower index comes first and is selected first.  The values output is read back from the row:
+// the sign bits of what is returned are the input's.
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -229,8 +232,12 @@ constexpr int kTopkThreads = 1024;
 constexpr int kTopkMaxN = 32768;
 constexpr int kTopkMaxK = 1024;
 
+// order-preserving key of a float: a NaN of either sign gets the highest key (the sign bit of a NaN means
+// nothing: x86 makes 0xffc00000 for inf - inf), and -0.0 the key of +0.0 (equal values: the index decides)
 __device__ __forceinline__ unsigned order_key(float x) {
   const unsigned b = __float_as_uint(x);
+  if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+  if (b == 0x80000000u) return 0x80000000u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 

@@ -1425,7 +1425,7 @@ def mha_core(qkv, n_seq, seq_len, num_heads):
 def topk_rows(x, k):
     """torch.topk(x, k, dim=1) for a 2-D fp32 device tensor as ONE launch (pave_topk_rows_f32):
     -> (values [rows, k], indices [rows, k] int64), sorted by value descending, ties by the
-    lower index.  x may be any strided 2-D view (no copy)."""
+    lower index (-0.0 == +0.0; a NaN of either sign ranks above +inf).  x may be any strided 2-D view (no copy)."""
     _require(isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
              and x.shape[0] > 0 and x.stride(1) > 0 and (x.shape[0] == 1 or x.stride(0) > 0),
              'topk_rows: x [rows, n] fp32 on the device, positive strides')
