@@ -455,6 +455,55 @@ int pave_draw_poses_nv12(const pave_draw_plan* plan, void* stream);
 int pave_draw_poses_bgr(const pave_draw_plan* plan, void* stream);
 
 /*
+ * Track ids: the poses of a frame linked to the poses of the frames before it (pavenet_amd/csrc/pave_track.hip; the
+ * rule is DESIGN section 14, integer-exact), one launch for `entries` frames of any of `cameras` cameras.  The plan
+ * is copied into the kernel's arguments.  One block per camera of the launch takes that camera's entries in plan
+ * order: entries of one camera are in time order.
+ *   kpts[i]    DEVICE [n[i], K, 3] fp32 (x, y, score);  bboxes[i] [n[i], 5] fp32;  keep[i] [n[i]] int32 or NULL
+ *   ids[i]     DEVICE [n[i]] int32, out: the track id of every pose, 0 = not tracked.  kpts, bboxes and ids may be
+ *              NULL where n[i] == 0 (the frame still counts: it advances the camera's clock and expires slots)
+ *   camera[i]  whose state entry i reads and writes;  scale[i] (sx, sy) as in pave_draw_plan
+ *   the state, DEVICE, read and written: track_id, track_last, track_area [cameras, M] int32, track_vis [cameras, M]
+ *              (bit k: key point k visible), track_kpts [cameras, M, K, 2] int32 quarter pixels; frame, next_id,
+ *              dropped [cameras] int32.  A slot with track_id 0 is free and its other fields are never read
+ *   scratch    DEVICE, PAVE_TRACK_MAX_FRAMES x 128 x 128 int64 (4 MiB): the pair keys of every block
+ *   C[k]       max(1, rint(ln(1 / match_thr) (2 sigma_k)^2 2^20)): key point k of a pair agrees iff
+ *              (d2_k << 20) <= C[k] (area_d + area_t)
+ * Refused with PAVE_E_ARG before any device call: a null plan, state tensor or scratch area, a null kpts, bboxes or
+ * ids where n[i] > 0, entries outside 1 .. 32, n[i] outside 0 .. 128, K outside 1 .. 32, M outside 1 .. 128, cameras
+ * outside 1 .. 4096, a camera index outside [0, cameras), a scale that is not positive and finite, a C[k] outside
+ * [1, 2^24), min_kpts outside 1 .. K, max_age < 0.  Coordinates are clamped by the rule: a plan that passes cannot
+ * address memory outside its tensors, whatever the pose values are.
+ */
+#define PAVE_TRACK_MAX_FRAMES 32
+#define PAVE_TRACK_MAX_POSES 128
+#define PAVE_TRACK_MAX_TRACKS 128
+#define PAVE_TRACK_MAX_K 32
+#define PAVE_TRACK_MAX_CAMERAS 4096
+typedef struct pave_track_plan {
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       ids[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int32_t*  track_id;
+  int32_t*  track_last;
+  int32_t*  track_kpts;
+  uint32_t* track_vis;
+  int32_t*  track_area;
+  int32_t*  frame;
+  int32_t*  next_id;
+  int32_t*  dropped;
+  long long* scratch;
+  int   C[PAVE_TRACK_MAX_K];
+  int entries, cameras, M, K, min_kpts, max_age;
+  float score_thr, kpt_thr;
+} pave_track_plan;
+int pave_track_poses(const pave_track_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

@@ -35,4 +35,7 @@ def __getattr__(name):
     if name in ('PoseStyle', 'draw_poses_nv12', 'draw_poses_bgr', 'bgr_to_yuv'):
         from . import render
         return getattr(render, name)
+    if name == 'PoseTracker':
+        from . import tracking
+        return tracking.PoseTracker
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -4,6 +4,8 @@
 * ``kpt2json`` / ``results2json``: COCO-style keypoint json of a list of per-image results,
   restated from opera/datasets/posetrack_video_pose.py:268-348 (the dataset methods
   ``_kpt2json`` / ``results2json``; only the keypoint branch is on this path).
+* ``posetrack_frame``: one frame of the PoseTrack evaluation json (``{'annolist': [frame, ...]}``,
+  posetrack_video_pose.py:478-491) with the track ids of ``tracking.PoseTracker`` where the reference writes 0.
 * ``load_checkpoint``: reads a reference checkpoint (``{'state_dict': ...}`` or a bare state
   dict, optional ``module.`` prefix from DDP, tools/test.py:226) into a model built here --
   the parameter names are the reference's own (tests/golden/state_dict_keys.json).
@@ -52,6 +54,27 @@ def results2json(results, img_ids, outfile_prefix, cat_ids=(1,)):
     with open(files['keypoints'], 'w') as f:
         json.dump(kpt_json, f)
     return files
+
+
+def posetrack_frame(image_name, imgnum, result, ids):
+    """One entry of a PoseTrack json's `annolist`: {'image': {'name': image_name}, 'imgnum': [imgnum], 'annorect':
+    [...]}, one annorect per tracked pose with 'annopoints': [{'point': [{'id': [k], 'x': [x], 'y': [y], 'score':
+    [s]} for every key point k]}], 'score': [box score] and 'track_id': [id].  result: one frame's (bboxes, labels,
+    kpts) tuple or dict(bboxes=, kpts=, keep=), device or host; ids: its int [N] track ids (PoseTracker.update).
+    Poses with id 0 (not tracked) are left out.  An output format: it copies to the host and so waits for the
+    device."""
+    from .render import _poses
+    kpts, bboxes, _ = _poses(result, 0, 'posetrack_frame')
+    ids = np.asarray(ids.detach().cpu() if isinstance(ids, torch.Tensor) else ids).reshape(-1)
+    if ids.shape[0] != kpts.shape[0]:
+        raise ValueError(f'posetrack_frame: {kpts.shape[0]} poses and {ids.shape[0]} ids')
+    kpts, bboxes = kpts.detach().cpu().numpy(), bboxes.detach().cpu().numpy()
+    annorect = []
+    for p in np.nonzero(ids)[0]:
+        points = [{'id': [k], 'x': [float(x)], 'y': [float(y)], 'score': [float(s)]}
+                  for k, (x, y, s) in enumerate(kpts[p])]
+        annorect.append({'annopoints': [{'point': points}], 'score': [float(bboxes[p, 4])], 'track_id': [int(ids[p])]})
+    return {'image': {'name': image_name}, 'imgnum': [int(imgnum)], 'annorect': annorect}
 
 
 def load_checkpoint(model, filename, map_location='cpu', strict=False):

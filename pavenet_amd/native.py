@@ -129,6 +129,24 @@ class DrawPlan(ctypes.Structure):
                 ('draw_boxes', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
 
 
+TRACK_MAX_FRAMES, TRACK_MAX_POSES, TRACK_MAX_TRACKS, TRACK_MAX_K, TRACK_MAX_CAMERAS = (
+    DEFINES['PAVE_TRACK_MAX_' + n] for n in ('FRAMES', 'POSES', 'TRACKS', 'K', 'CAMERAS'))
+
+
+class TrackPlan(ctypes.Structure):
+    """`pave_track_plan` of include/pave_hip.h (the by-value argument of pave_track_poses)."""
+    _fields_ = [('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('n', ctypes.c_int * TRACK_MAX_FRAMES), ('camera', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES), ('track_id', ctypes.c_void_p),
+                ('track_last', ctypes.c_void_p), ('track_kpts', ctypes.c_void_p), ('track_vis', ctypes.c_void_p),
+                ('track_area', ctypes.c_void_p), ('frame', ctypes.c_void_p), ('next_id', ctypes.c_void_p),
+                ('dropped', ctypes.c_void_p), ('scratch', ctypes.c_void_p), ('C', ctypes.c_int * TRACK_MAX_K),
+                ('entries', ctypes.c_int), ('cameras', ctypes.c_int), ('M', ctypes.c_int), ('K', ctypes.c_int),
+                ('min_kpts', ctypes.c_int), ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float),
+                ('kpt_thr', ctypes.c_float)]
+
+
 _lib = None
 
 

@@ -620,6 +620,106 @@ def draw_poses(kind, items, colors, edges, K, *, thickness=4, radius=4, score_th
         _launch(entry, 'draw_poses', dev, ctypes.byref(plan))
 
 
+_TRACK_STATE = (('id', 1), ('last', 1), ('kpts', 2), ('vis', 1), ('area', 1), ('frame', 0), ('next_id', 0),
+                ('dropped', 0))   # name, kind: 0 [cameras], 1 [cameras, M], 2 [cameras, M, K, 2]
+
+
+def track_scratch(device):
+    """The pair-key area of pave_track_poses: 32 blocks x 128 x 128 int64 (4 MiB), allocated once per tracker."""
+    return torch.empty((native.TRACK_MAX_FRAMES, native.TRACK_MAX_POSES, native.TRACK_MAX_TRACKS), dtype=torch.int64,
+                       device=device)
+
+
+def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0.3, kpt_thr=0.):
+    """Track ids for frames of poses, one launch per 32 frames (pave_track_poses; the rule is DESIGN section 14).
+    entries: one (kpts [N, K, 3] fp32, bboxes [N, 5] fp32, keep [N] int32 or None, camera, (sx, sy)) per frame, N <=
+    128, the frames of one camera in time order; state: int32 device tensors id, last, vis, area [cameras, M], kpts
+    [cameras, M, K, 2], frame, next_id, dropped [cameras], read and written; scratch: track_scratch(device); C: K
+    pair constants in [1, 2^24).  Returns one int32 [N] tensor of ids per entry.  Shapes, types and ranges raise
+    ValueError before anything is asked of a device."""
+    who = 'track_poses'
+    entries = list(entries)
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name, _ in _TRACK_STATE):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(n for n, _ in _TRACK_STATE)}')
+    if state['kpts'].dim() != 4 or state['kpts'].shape[3] != 2:
+        raise ValueError(f'{who}: state kpts must be [cameras, M, K, 2], got {tuple(state["kpts"].shape)}')
+    cameras, M, K = state['kpts'].shape[:3]
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= M <= native.TRACK_MAX_TRACKS
+            and 1 <= K <= native.TRACK_MAX_K):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS}, M in 1 .. {native.TRACK_MAX_TRACKS} and K '
+                         f'in 1 .. {native.TRACK_MAX_K}, got {cameras}, {M} and {K}')
+    dev = state['kpts'].device
+    for name, kind in _TRACK_STATE:
+        t = state[name]
+        want = ((cameras,), (cameras, M), (cameras, M, K, 2))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    if not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.int64 and scratch.is_contiguous()
+            and scratch.numel() >= native.TRACK_MAX_FRAMES * native.TRACK_MAX_POSES * native.TRACK_MAX_TRACKS):
+        raise ValueError(f'{who}: scratch is track_scratch(device)')
+    C = [int(c) for c in C]
+    if len(C) != K or any(not 1 <= c < 1 << 24 for c in C):
+        raise ValueError(f'{who}: C holds K = {K} pair constants in [1, 2^24)')
+    if int(min_kpts) != min_kpts or not 1 <= min_kpts <= K:
+        raise ValueError(f'{who}: min_kpts in 1 .. K = {K}, got {min_kpts!r}')
+    if int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    checked = []
+    for i, entry in enumerate(entries):
+        if not (isinstance(entry, (tuple, list)) and len(entry) == 5):
+            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, camera, (sx, sy))')
+        kpts, bboxes, keep, camera, scale = entry
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
+        if N > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+        try:
+            sx, sy = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
+        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep)):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
+        checked.append((kpts, bboxes, keep, int(camera), sx, sy, N))
+    # the shapes are right: now where the tensors live
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(t.device != dev for t in [state[n] for n, _ in _TRACK_STATE] + [scratch]):
+        raise ValueError(f'{who}: the state tensors and the scratch area must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if any(t is not None and t.device != dev for t in c[:3]):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    ids = [torch.empty((c[6],), dtype=torch.int32, device=dev) for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.TrackPlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (kpts, bboxes, keep, camera, sx, sy, N) in enumerate(part):
+            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+                _ptr(keep) or None, ids[at + i].data_ptr() or None
+            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+        plan.track_id, plan.track_last, plan.track_kpts, plan.track_vis, plan.track_area = (
+            state[n].data_ptr() for n in ('id', 'last', 'kpts', 'vis', 'area'))
+        plan.frame, plan.next_id, plan.dropped = (state[n].data_ptr() for n in ('frame', 'next_id', 'dropped'))
+        plan.scratch = scratch.data_ptr()
+        for k, c in enumerate(C):
+            plan.C[k] = c
+        plan.entries, plan.cameras, plan.M, plan.K = len(part), cameras, M, K
+        plan.min_kpts, plan.max_age, plan.score_thr, plan.kpt_thr = int(min_kpts), int(max_age), float(score_thr), \
+            float(kpt_thr)
+        _launch('pave_track_poses', who, dev, ctypes.byref(plan))
+    return ids
+
+
 def fuse_sum_nhwc(terms, relu=True):
     """HRNet fuse layer in one pass (pave_fuse_sum_nhwc_f32): terms = [(map, shift), ...] (1..4), map
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones
