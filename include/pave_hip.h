@@ -455,6 +455,35 @@ int pave_draw_poses_nv12(const pave_draw_plan* plan, void* stream);
 int pave_draw_poses_bgr(const pave_draw_plan* plan, void* stream);
 
 /*
+ * Poses drawn with their track ids (the same kernel source; DESIGN section 13, "Track ids in the picture"): a pose
+ * whose id is >= 1 takes a colour chosen by the id and a plate with the id in decimal digits above its box.
+ *   base       everything of pave_draw_plan, with the same meaning and the same refusals
+ *   ids[i]     DEVICE [n_poses[i]] int32 (what pave_track_poses wrote) or NULL: surface i is drawn by base alone
+ *   palette[t] rows 0 .. 31: the colour of id v is row (v - 1) % 32; row 32: the ink of the digits; 3 bytes each,
+ *              stored as they are, one table per (matrix, range) pair as for color
+ *   font[d]    the 5 x 7 face of digit d: 7 rows, bit 4 of a row is its left-most pixel
+ *   label_scale  g in 0 .. 8: a font pixel is g x g picture pixels; 0: colours only, no labels
+ *   untracked_skip  0: a pose with ids[i][p] <= 0 is drawn by base alone;  1: it is not drawn
+ * A tracked pose's 4 box edges and E limbs take its palette row, its K discs keep base.color.  Its label, when
+ * g >= 1, with n the number of decimal digits of the id and (X1, Y1, X2, Y2) its quantised box: ax = min(X1, X2) >> 2,
+ * ay = max((min(Y1, Y2) >> 2) - 9 g, 0); the plate covers the g (6 n + 1) x 9 g pixels from (ax, ay), the ink the set
+ * bits of the digits' faces, 6 g apart, from (ax + g, ay + g).  Primitive ids: plate n_poses (4 + E + K) + 2 p, ink
+ * that + 1, so labels lie above every skeleton of their surface; the largest-id rule and the writes are base's.
+ * Refused with PAVE_E_ARG before any device call: whatever pave_draw_poses_* refuses in base, a label_scale outside
+ * 0 .. 8, an untracked_skip outside {0, 1}, a font row with bits above the low 5.  Id values need no check.
+ */
+#define PAVE_DRAW_PALETTE 32
+typedef struct pave_draw_ids_plan {
+  pave_draw_plan base;
+  const int32_t* ids[PAVE_DRAW_MAX_SURFACES];
+  uint8_t        palette[PAVE_DRAW_MAX_TABLES][PAVE_DRAW_PALETTE + 1][3];
+  uint8_t        font[10][7];
+  int label_scale, untracked_skip;
+} pave_draw_ids_plan;
+int pave_draw_tracks_nv12(const pave_draw_ids_plan* plan, void* stream);
+int pave_draw_tracks_bgr(const pave_draw_ids_plan* plan, void* stream);
+
+/*
  * Track ids: the poses of a frame linked to the poses of the frames before it (pavenet_amd/csrc/pave_track.hip; the
  * rule is DESIGN section 14, integer-exact), one launch for `entries` frames of any of `cameras` cameras.  The plan
  * is copied into the kernel's arguments.  One block per camera of the launch takes that camera's entries in plan

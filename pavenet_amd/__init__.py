@@ -32,7 +32,7 @@ def __getattr__(name):
     if name in ('LiveVideoPose', 'MultiLiveVideoPose', 'CameraRing'):
         from . import live
         return getattr(live, name)
-    if name in ('PoseStyle', 'draw_poses_nv12', 'draw_poses_bgr', 'bgr_to_yuv'):
+    if name in ('PoseStyle', 'TrackStyle', 'draw_poses_nv12', 'draw_poses_bgr', 'bgr_to_yuv'):
         from . import render
         return getattr(render, name)
     if name == 'PoseTracker':

@@ -129,6 +129,16 @@ class DrawPlan(ctypes.Structure):
                 ('draw_boxes', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
 
 
+DRAW_PALETTE = DEFINES['PAVE_DRAW_PALETTE']
+
+
+class DrawIdsPlan(ctypes.Structure):
+    """`pave_draw_ids_plan` of include/pave_hip.h (the by-value argument of pave_draw_tracks_nv12 / _bgr)."""
+    _fields_ = [('base', DrawPlan), ('ids', ctypes.c_void_p * DRAW_MAX_SURFACES),
+                ('palette', ((ctypes.c_uint8 * 3) * (DRAW_PALETTE + 1)) * DRAW_MAX_TABLES),
+                ('font', (ctypes.c_uint8 * 7) * 10), ('label_scale', ctypes.c_int), ('untracked_skip', ctypes.c_int)]
+
+
 TRACK_MAX_FRAMES, TRACK_MAX_POSES, TRACK_MAX_TRACKS, TRACK_MAX_K, TRACK_MAX_CAMERAS = (
     DEFINES['PAVE_TRACK_MAX_' + n] for n in ('FRAMES', 'POSES', 'TRACKS', 'K', 'CAMERAS'))
 

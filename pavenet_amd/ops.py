@@ -530,6 +530,97 @@ def scatter_rows(srcs, dsts, rows):
         _launch('pave_scatter_rows_f32', 'scatter_rows', dev, ctypes.byref(plan))
 
 
+def _draw_shapes(who, kind, items, colors, edges, K, thickness, radius):
+    """The checks of shapes, types and ranges draw_poses and draw_tracks share (an item's first seven entries), all
+    ValueError -> (items, edges, K, geometry, the tables' bytes)."""
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
+    items, edges, K = list(items), [(int(a), int(b)) for a, b in edges], int(K)
+    if not 1 <= K <= native.DRAW_MAX_K or len(edges) > native.DRAW_MAX_E:
+        raise ValueError(f'{who}: K in 1 .. {native.DRAW_MAX_K} and at most {native.DRAW_MAX_E} edges, got K = {K} '
+                         f'and {len(edges)} edges')
+    if any(not (0 <= a < K and 0 <= b < K) for a, b in edges):
+        raise ValueError(f'{who}: an edge index outside [0, {K})')
+    if not 1 <= int(thickness) <= 32 or not 0 <= int(radius) <= 32:
+        raise ValueError(f'{who}: thickness in 1 .. 32 and radius in 0 .. 32, got {thickness} and {radius}')
+    try:   # (a table may come as the 195 bytes themselves: PoseStyle caches them)
+        colors = [tab if isinstance(tab, bytes) else bytes(int(c) for row in tab for c in (row if len(row) == 3 else ()))
+                  for tab in colors]
+    except (TypeError, ValueError):
+        colors = []
+    if not 1 <= len(colors) <= native.DRAW_MAX_TABLES or any(len(tab) != 3 * native.DRAW_COLORS for tab in colors):
+        raise ValueError(f'{who}: colors are 1 .. {native.DRAW_MAX_TABLES} tables of {native.DRAW_COLORS} x 3 bytes')
+    if not items:
+        raise ValueError(f'{who}: no surface')
+    geometry = []
+    for i, it in enumerate(items):
+        surf, width, kpts, bboxes, keep, scale, table = it[:7]
+        if not (isinstance(surf, torch.Tensor) and surf.dtype == torch.uint8):
+            raise ValueError(f'{who}: surface {i} must be a uint8 tensor')
+        if kind == 'nv12':
+            if surf.dim() != 2:
+                raise ValueError(f'{who}: surface {i} must be [H * 3 // 2, pitch], got {tuple(surf.shape)}')
+            rows, pitch = surf.shape
+            H, W, row_bytes = rows * 2 // 3, int(width), int(width)
+            if rows % 3 != 0 or H % 2 != 0 or H <= 0:
+                raise ValueError(f'{who}: surface {i}: {rows} rows are not the 3/2 of an even height')
+            if W <= 0 or W % 2 != 0:
+                raise ValueError(f'{who}: surface {i}: width {W} must be even and positive')
+        else:
+            if surf.dim() != 3 or surf.shape[2] != 3 or surf.shape[0] < 1 or surf.shape[1] < 1:
+                raise ValueError(f'{who}: surface {i} must be [H, W, 3], got {tuple(surf.shape)}')
+            H, W = surf.shape[:2]
+            pitch = row_bytes = 3 * W
+        if row_bytes > pitch:
+            raise ValueError(f'{who}: surface {i}: width {W} exceeds the pitch {pitch}')
+        if W > native.DRAW_MAX_SIZE or H > native.DRAW_MAX_SIZE:
+            raise ValueError(f'{who}: surface {i}: {W} x {H} exceeds {native.DRAW_MAX_SIZE} x {native.DRAW_MAX_SIZE}')
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'{who}: kpts of surface {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'{who}: bboxes of surface {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'{who}: keep of surface {i} must be a [{N}] int32 tensor')
+        if N > native.DRAW_MAX_POSES:
+            raise ValueError(f'{who}: surface {i} has {N} poses, at most {native.DRAW_MAX_POSES}')
+        sx, sy = (float(v) for v in scale)
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'{who}: the scale of surface {i} must be positive and finite, got {(sx, sy)}')
+        if not 0 <= int(table) < len(colors):
+            raise ValueError(f'{who}: surface {i} names colour table {table} of {len(colors)}')
+        geometry.append((int(pitch), int(W), int(H), N, sx, sy, int(table)))
+    return items, edges, K, geometry, b''.join(colors)   # [tables][65][3], the plan's layout
+
+
+def _draw_device(who, items):
+    """Where the tensors of checked items live: one HIP device."""
+    dev = items[0][0].device
+    for i, it in enumerate(items):
+        for t, name in ((it[0], 'surface'), (it[2], 'kpts'), (it[3], 'bboxes'), (it[4], 'keep')):
+            if t is not None:
+                _dev(t, f'{who}: {name} of surface {i}')
+                _require(t.device == dev, f'{who}: all tensors on one device')
+    return dev
+
+
+def _draw_fill(plan, part, geometry, raw_colors, edges, K, thickness, radius, score_thr, kpt_thr, draw_boxes):
+    """A pave_draw_plan for the surfaces `part`."""
+    for i, it in enumerate(part):
+        pitch, W, H, N, sx, sy, table = geometry[i]
+        plan.dst[i], plan.kpts[i], plan.bboxes[i], plan.keep[i] = it[0].data_ptr(), it[2].data_ptr(), \
+            it[3].data_ptr(), _ptr(it[4])
+        plan.pitch[i], plan.width[i], plan.height[i], plan.n_poses[i] = pitch, W, H, N
+        plan.scale[i][0], plan.scale[i][1], plan.table[i] = sx, sy, table
+    ctypes.memmove(plan.color, raw_colors, len(raw_colors))
+    for e, (a, b) in enumerate(edges):
+        plan.edge[e][0], plan.edge[e][1] = a, b
+    plan.n, plan.K, plan.E, plan.thickness, plan.radius = len(part), K, len(edges), int(thickness), int(radius)
+    plan.draw_boxes, plan.score_thr, plan.kpt_thr = int(bool(draw_boxes)), float(score_thr), float(kpt_thr)
+
+
 def draw_poses(kind, items, colors, edges, K, *, thickness=4, radius=4, score_thr=0.3, kpt_thr=0., draw_boxes=False):
     """Poses drawn into surfaces in place, one launch per 32 surfaces (pave_draw_poses_nv12 / _bgr; the rule is
     DESIGN section 13).  kind 'nv12': a surface is a [H * 3 // 2, pitch] uint8 tensor whose first `width` columns are
@@ -537,87 +628,77 @@ def draw_poses(kind, items, colors, edges, K, *, thickness=4, radius=4, score_th
     fp32, bboxes [N, 5] fp32, keep [N] int32 or None, (sx, sy), table) per surface; colors [tables <= 4, 65, 3] bytes
     stored as they are (row 0 boxes, 1 .. 32 limbs, 33 .. 64 key points; a table nested or as its 195 bytes); edges: E <= 32 pairs of key-point indices.
     Shapes, types and ranges raise ValueError before anything is asked of a device."""
-    if kind not in ('nv12', 'bgr'):
-        raise ValueError(f"draw_poses: kind {kind!r} is not 'nv12' or 'bgr'")
-    items, edges, K = list(items), [(int(a), int(b)) for a, b in edges], int(K)
-    if not 1 <= K <= native.DRAW_MAX_K or len(edges) > native.DRAW_MAX_E:
-        raise ValueError(f'draw_poses: K in 1 .. {native.DRAW_MAX_K} and at most {native.DRAW_MAX_E} edges, got K = {K} '
-                         f'and {len(edges)} edges')
-    if any(not (0 <= a < K and 0 <= b < K) for a, b in edges):
-        raise ValueError(f'draw_poses: an edge index outside [0, {K})')
-    if not 1 <= int(thickness) <= 32 or not 0 <= int(radius) <= 32:
-        raise ValueError(f'draw_poses: thickness in 1 .. 32 and radius in 0 .. 32, got {thickness} and {radius}')
-    try:   # (a table may come as the 195 bytes themselves: PoseStyle caches them)
-        colors = [tab if isinstance(tab, bytes) else bytes(int(c) for row in tab for c in (row if len(row) == 3 else ()))
-                  for tab in colors]
-    except (TypeError, ValueError):
-        colors = []
-    if not 1 <= len(colors) <= native.DRAW_MAX_TABLES or any(len(tab) != 3 * native.DRAW_COLORS for tab in colors):
-        raise ValueError(f'draw_poses: colors are 1 .. {native.DRAW_MAX_TABLES} tables of {native.DRAW_COLORS} x 3 bytes')
-    if not items:
-        raise ValueError('draw_poses: no surface')
-    geometry = []
-    for i, (surf, width, kpts, bboxes, keep, scale, table) in enumerate(items):
-        if not (isinstance(surf, torch.Tensor) and surf.dtype == torch.uint8):
-            raise ValueError(f'draw_poses: surface {i} must be a uint8 tensor')
-        if kind == 'nv12':
-            if surf.dim() != 2:
-                raise ValueError(f'draw_poses: surface {i} must be [H * 3 // 2, pitch], got {tuple(surf.shape)}')
-            rows, pitch = surf.shape
-            H, W, row_bytes = rows * 2 // 3, int(width), int(width)
-            if rows % 3 != 0 or H % 2 != 0 or H <= 0:
-                raise ValueError(f'draw_poses: surface {i}: {rows} rows are not the 3/2 of an even height')
-            if W <= 0 or W % 2 != 0:
-                raise ValueError(f'draw_poses: surface {i}: width {W} must be even and positive')
-        else:
-            if surf.dim() != 3 or surf.shape[2] != 3 or surf.shape[0] < 1 or surf.shape[1] < 1:
-                raise ValueError(f'draw_poses: surface {i} must be [H, W, 3], got {tuple(surf.shape)}')
-            H, W = surf.shape[:2]
-            pitch = row_bytes = 3 * W
-        if row_bytes > pitch:
-            raise ValueError(f'draw_poses: surface {i}: width {W} exceeds the pitch {pitch}')
-        if W > native.DRAW_MAX_SIZE or H > native.DRAW_MAX_SIZE:
-            raise ValueError(f'draw_poses: surface {i}: {W} x {H} exceeds {native.DRAW_MAX_SIZE} x {native.DRAW_MAX_SIZE}')
-        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
-                and tuple(kpts.shape[1:]) == (K, 3)):
-            raise ValueError(f'draw_poses: kpts of surface {i} must be a [N, {K}, 3] float32 tensor')
-        N = kpts.shape[0]
-        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
-            raise ValueError(f'draw_poses: bboxes of surface {i} must be a [{N}, 5] float32 tensor')
-        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
-                                     and tuple(keep.shape) == (N,)):
-            raise ValueError(f'draw_poses: keep of surface {i} must be a [{N}] int32 tensor')
-        if N > native.DRAW_MAX_POSES:
-            raise ValueError(f'draw_poses: surface {i} has {N} poses, at most {native.DRAW_MAX_POSES}')
-        sx, sy = (float(v) for v in scale)
-        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
-            raise ValueError(f'draw_poses: the scale of surface {i} must be positive and finite, got {(sx, sy)}')
-        if not 0 <= int(table) < len(colors):
-            raise ValueError(f'draw_poses: surface {i} names colour table {table} of {len(colors)}')
-        geometry.append((int(pitch), int(W), int(H), N, sx, sy, int(table)))
-    dev = items[0][0].device
-    for i, (surf, _, kpts, bboxes, keep, _, _) in enumerate(items):
-        for t, name in ((surf, 'surface'), (kpts, 'kpts'), (bboxes, 'bboxes'), (keep, 'keep')):
-            if t is not None:
-                _dev(t, f'draw_poses: {name} of surface {i}')
-                _require(t.device == dev, 'draw_poses: all tensors on one device')
+    items, edges, K, geometry, raw_colors = _draw_shapes('draw_poses', kind, items, colors, edges, K, thickness, radius)
+    dev = _draw_device('draw_poses', items)
     entry = 'pave_draw_poses_nv12' if kind == 'nv12' else 'pave_draw_poses_bgr'
-    raw_colors = b''.join(colors)   # [tables][65][3], the plan's layout
     for at in range(0, len(items), native.DRAW_MAX_SURFACES):
         plan = native.DrawPlan()
         part = items[at:at + native.DRAW_MAX_SURFACES]
-        for i, (surf, _, kpts, bboxes, keep, _, _) in enumerate(part):
-            pitch, W, H, N, sx, sy, table = geometry[at + i]
-            plan.dst[i], plan.kpts[i], plan.bboxes[i], plan.keep[i] = surf.data_ptr(), kpts.data_ptr(), \
-                bboxes.data_ptr(), _ptr(keep)
-            plan.pitch[i], plan.width[i], plan.height[i], plan.n_poses[i] = pitch, W, H, N
-            plan.scale[i][0], plan.scale[i][1], plan.table[i] = sx, sy, table
-        ctypes.memmove(plan.color, raw_colors, len(raw_colors))
-        for e, (a, b) in enumerate(edges):
-            plan.edge[e][0], plan.edge[e][1] = a, b
-        plan.n, plan.K, plan.E, plan.thickness, plan.radius = len(part), K, len(edges), int(thickness), int(radius)
-        plan.draw_boxes, plan.score_thr, plan.kpt_thr = int(bool(draw_boxes)), float(score_thr), float(kpt_thr)
+        _draw_fill(plan, part, geometry[at:at + len(part)], raw_colors, edges, K, thickness, radius, score_thr, kpt_thr,
+                   draw_boxes)
         _launch(entry, 'draw_poses', dev, ctypes.byref(plan))
+
+
+def draw_tracks(kind, items, colors, palettes, font, edges, K, *, label_scale=2, untracked='style', thickness=4,
+                radius=4, score_thr=0.3, kpt_thr=0., draw_boxes=False):
+    """draw_poses with track ids in the picture, one launch per 32 surfaces (pave_draw_tracks_nv12 / _bgr; DESIGN
+    section 13, "Track ids in the picture").  items: draw_poses' seven entries and `ids`: a contiguous int32 [N]
+    tensor on the surface's device (what PoseTracker.update returns), or None for a surface drawn as draw_poses
+    draws it.  palettes: one per colour table, 33 x 3 bytes stored as they are (rows 0 .. 31: id v takes row
+    (v - 1) % 32; row 32: the digits' ink; nested or as the 99 bytes); font: 10 digits x 7 rows of 5 bits (bit 4 the
+    left-most pixel); label_scale 0 .. 8 (0: colours only); untracked 'style' | 'skip': a pose with id <= 0 is drawn
+    as draw_poses draws it, or not at all.  Shapes, types and ranges raise ValueError before anything is asked of a
+    device."""
+    who = 'draw_tracks'
+    items = list(items)
+    if any(not (isinstance(it, (tuple, list)) and len(it) == 8) for it in items):
+        raise ValueError(f'{who}: an item is (surface, width, kpts, bboxes, keep, (sx, sy), table, ids)')
+    if isinstance(label_scale, bool) or not isinstance(label_scale, int) or not 0 <= label_scale <= 8:
+        raise ValueError(f'{who}: label_scale is an integer in 0 .. 8, got {label_scale!r}')
+    if untracked not in ('style', 'skip'):
+        raise ValueError(f"{who}: untracked {untracked!r} is not 'style' or 'skip'")
+    try:
+        font = [[int(r) for r in rows] for rows in font]
+    except (TypeError, ValueError):
+        font = []
+    if len(font) != 10 or any(len(rows) != 7 or any(not 0 <= r < 32 for r in rows) for rows in font):
+        raise ValueError(f'{who}: font is 10 digits of 7 rows of 5 bits')
+    rows = native.DRAW_PALETTE + 1
+    try:
+        palettes = [tab if isinstance(tab, bytes) else bytes(int(c) for row in tab for c in (row if len(row) == 3 else ()))
+                    for tab in palettes]
+    except (TypeError, ValueError):
+        palettes = []
+    if not 1 <= len(palettes) <= native.DRAW_MAX_TABLES or any(len(tab) != 3 * rows for tab in palettes):
+        raise ValueError(f'{who}: palettes are 1 .. {native.DRAW_MAX_TABLES} tables of {rows} x 3 bytes')
+    items, edges, K, geometry, raw_colors = _draw_shapes(who, kind, items, colors, edges, K, thickness, radius)
+    if len(palettes) != len(raw_colors) // (3 * native.DRAW_COLORS):
+        raise ValueError(f'{who}: one palette per colour table ({len(raw_colors) // (3 * native.DRAW_COLORS)}), got '
+                         f'{len(palettes)}')
+    for i, it in enumerate(items):
+        ids, N = it[7], geometry[i][3]
+        if ids is None:
+            continue
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
+            raise ValueError(f'{who}: ids of surface {i} must be a [{N}] int32 tensor or None')
+        if not ids.is_contiguous():
+            raise ValueError(f'{who}: ids of surface {i} must be contiguous')
+        if ids.device != it[0].device:
+            raise ValueError(f'{who}: ids of surface {i} are on {ids.device}, the surface on {it[0].device}')
+    dev = _draw_device(who, items)
+    entry = 'pave_draw_tracks_nv12' if kind == 'nv12' else 'pave_draw_tracks_bgr'
+    raw_palettes, raw_font = b''.join(palettes), bytes(r for rows in font for r in rows)
+    for at in range(0, len(items), native.DRAW_MAX_SURFACES):
+        plan = native.DrawIdsPlan()
+        part = items[at:at + native.DRAW_MAX_SURFACES]
+        _draw_fill(plan.base, part, geometry[at:at + len(part)], raw_colors, edges, K, thickness, radius, score_thr,
+                   kpt_thr, draw_boxes)
+        for i, it in enumerate(part):
+            plan.ids[i] = _ptr(it[7])
+        ctypes.memmove(plan.palette, raw_palettes, len(raw_palettes))
+        ctypes.memmove(plan.font, raw_font, len(raw_font))
+        plan.label_scale, plan.untracked_skip = int(label_scale), int(untracked == 'skip')
+        _launch(entry, who, dev, ctypes.byref(plan))
 
 
 _TRACK_STATE = (('id', 1), ('last', 1), ('kpts', 2), ('vis', 1), ('area', 1), ('frame', 0), ('next_id', 0),

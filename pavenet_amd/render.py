@@ -5,7 +5,9 @@ reference's public method on top of the latter (opera/models/detectors/videopose
 the host there).  Drawing is in place, one launch per 32 surfaces, and reads no device value on the host: the
 fixed-shape ``dict(bboxes=, kpts=, keep=)`` of ``head.get_bboxes`` is drawn without the sync of ``results_to_list``.
 
-Hard-edged integer coverage (no anti-aliasing, no blending, no text).  Skeletons are written from the key-point
+Hard-edged integer coverage (no anti-aliasing, no blending; the only text is the digits of a track id).  With
+``ids=`` (what ``PoseTracker.update`` returns, still on the device) a tracked pose takes a colour chosen by its id and
+a small plate with the id above its box (``TrackStyle``).  Skeletons are written from the key-point
 orders of ``keypoints.py`` (PoseTrack: nose, head bottom, head top, then left / right shoulder, elbow, wrist, hip,
 knee, ankle); the palette is this project's: left limbs warm, right limbs cool, the middle green.
 """
@@ -26,6 +28,27 @@ _CROWDPOSE = ([(12, 13), (13, 0), (13, 1), (0, 2), (2, 4), (1, 3), (3, 5), (0, 6
 LIMB_COLORS = {'l': (48, 132, 255), 'r': (255, 168, 56), 'c': (96, 214, 120)}
 KPT_COLORS = {'l': (120, 186, 255), 'r': (255, 208, 140), 'c': (170, 240, 186)}
 BBOX_COLOR = (72, 101, 241)
+# BGR, one per track: id v takes row (v - 1) % 32.  Hues 11 / 32 of the circle apart from one id to the next, two
+# brightness and two saturation levels; every colour is at least 64 of 255 darker in BT.601 luma than white ink.
+TRACK_PALETTE = (
+    (36, 36, 242), (37, 184, 28), (242, 97, 115), (73, 94, 184), (88, 242, 36), (184, 28, 76), (97, 151, 242),
+    (122, 184, 73), (242, 36, 139), (28, 115, 184), (172, 221, 89), (184, 73, 149), (34, 178, 226), (154, 184, 28),
+    (242, 97, 224), (73, 177, 184), (236, 236, 35), (174, 28, 184), (77, 194, 179), (184, 163, 73), (191, 36, 242),
+    (28, 184, 135), (242, 188, 97), (135, 73, 184), (34, 227, 130), (184, 96, 28), (151, 97, 242), (73, 184, 108),
+    (242, 88, 36), (57, 28, 184), (91, 227, 108), (184, 80, 73))
+# The one definition of the digit face: 10 digits x 7 rows of 5 bits, bit 4 the left-most pixel.  It travels to the
+# kernel in the plan and to the oracle as an argument.
+DIGIT_FONT = tuple(tuple(int(row.replace('.', '0').replace('#', '1'), 2) for row in face.split()) for face in (
+    '.###. #...# #..## #.#.# ##..# #...# .###.',
+    '..#.. .##.. ..#.. ..#.. ..#.. ..#.. .###.',
+    '.###. #...# ....# ...#. ..#.. .#... #####',
+    '####. ....# ....# .###. ....# ....# ####.',
+    '...#. ..##. .#.#. #..#. ##### ...#. ...#.',
+    '##### #.... ####. ....# ....# #...# .###.',
+    '..##. .#... #.... ####. #...# #...# .###.',
+    '##### ....# ...#. ..#.. .#... .#... .#...',
+    '.###. #...# #...# .###. #...# #...# .###.',
+    '.###. #...# #...# .#### ....# ...#. .##..'))
 
 
 def _builtin(K):
@@ -128,6 +151,42 @@ class PoseStyle:
         return cache[key]
 
 
+class TrackStyle(PoseStyle):
+    """PoseStyle for poses with track ids: a pose with id v >= 1 has its limbs (and box) in `palette[(v - 1) % 32]`
+    (32 BGR colours; the key points keep the style's colours) and, with `label_scale` g in 1 .. 8, a plate of that
+    colour above its box with v in decimal digits of `label_color`, a font pixel g x g picture pixels; g = 0: colours
+    only.  `untracked`: a pose with id <= 0 is drawn as PoseStyle draws it ('style') or not at all ('skip').  The
+    other arguments are PoseStyle's."""
+
+    def __init__(self, K, palette=TRACK_PALETTE, label_scale=2, label_color=(255, 255, 255), untracked='style', **kw):
+        super().__init__(K, **kw)
+        try:
+            palette = list(palette)
+        except TypeError:
+            palette = []
+        if len(palette) != native.DRAW_PALETTE:
+            raise ValueError(f'TrackStyle: palette is {native.DRAW_PALETTE} colours, got {len(palette)}')
+        self.palette = [_bgr_triple(c, 'TrackStyle: a palette colour') for c in palette]
+        self.label_color = _bgr_triple(label_color, 'TrackStyle: label_color')
+        if isinstance(label_scale, bool) or not isinstance(label_scale, (int, np.integer)) or not 0 <= label_scale <= 8:
+            raise ValueError(f'TrackStyle: label_scale is an integer in 0 .. 8, got {label_scale!r}')
+        if untracked not in ('style', 'skip'):
+            raise ValueError(f"TrackStyle: untracked is 'style' or 'skip', got {untracked!r}")
+        self.label_scale, self.untracked = int(label_scale), untracked
+
+    def palette_bytes(self, matrix=None, full_range=False):
+        """The 99 bytes of the ids plan (rows 0 .. 31 the palette, row 32 the ink): BGR (matrix None) or the
+        (Y, U, V) of a matrix and range; kept per colour set like table_bytes."""
+        key = ('palette', matrix, bool(full_range), tuple(self.palette), self.label_color)
+        cache = self.__dict__.setdefault('_tables', {})
+        if key not in cache:
+            table = np.asarray(self.palette + [self.label_color], dtype=np.uint8)
+            if matrix is not None:
+                table = bgr_to_yuv(table, matrix, full_range)
+            cache[key] = table.tobytes()
+        return cache[key]
+
+
 def _per_surface(v, n, name, scalar, who):
     if isinstance(v, scalar):
         return [v] * n
@@ -189,7 +248,8 @@ def _poses(result, i, who):
     return kpts.contiguous(), bboxes.contiguous(), None if keep is None else keep.contiguous()
 
 
-def _gather(surfaces, results, style, who):
+def _gather(surfaces, results, style, who, ids=None):
+    """-> (surfaces, poses, style, ids): lists of one entry per surface; ids None when the call has none."""
     single = isinstance(surfaces, torch.Tensor)
     surf = [surfaces] if single else (list(surfaces) if isinstance(surfaces, (list, tuple)) else None)
     if not surf:
@@ -199,6 +259,17 @@ def _gather(surfaces, results, style, who):
         raise ValueError(f'{who}: one result per surface ({len(surf)})')
     poses = [_poses(r, i, who) for i, r in enumerate(results)]
     K = poses[0][0].shape[1]
+    if ids is not None:
+        ids = [ids] if single and isinstance(ids, torch.Tensor) else (list(ids) if isinstance(ids, (list, tuple)) else None)
+        if ids is None or len(ids) != len(surf):
+            raise ValueError(f'{who}: ids is one tensor for one surface, or a list of a tensor or None per surface '
+                             f'({len(surf)})')
+        if any(not (v is None or isinstance(v, torch.Tensor)) for v in ids):
+            raise ValueError(f'{who}: an entry of ids is an int32 tensor or None')
+        if style is None:
+            style = TrackStyle(K)
+        if not isinstance(style, TrackStyle):
+            raise ValueError(f'{who}: with ids, style is a TrackStyle')
     if style is None:
         style = PoseStyle(K)
     if not isinstance(style, PoseStyle):
@@ -206,23 +277,31 @@ def _gather(surfaces, results, style, who):
     for i, (kpts, _, _) in enumerate(poses):
         if kpts.shape[1] != style.K:
             raise ValueError(f'{who}: results[{i}] has K = {kpts.shape[1]}, the style K = {style.K}')
-    return surf, poses, style
+    return surf, poses, style, ids
 
 
-def _draw(kind, items, tables, style):
-    ops.draw_poses(kind, items, tables, style.edges, style.K, thickness=style.thickness, radius=style.radius,
-                   score_thr=style.score_thr, kpt_thr=style.kpt_thr, draw_boxes=style.draw_boxes)
+def _draw(kind, items, tables, style, ids=None, palettes=None):
+    kw = dict(thickness=style.thickness, radius=style.radius, score_thr=style.score_thr, kpt_thr=style.kpt_thr,
+              draw_boxes=style.draw_boxes)
+    if ids is None:
+        return ops.draw_poses(kind, items, tables, style.edges, style.K, **kw)
+    ops.draw_tracks(kind, [it + (v,) for it, v in zip(items, ids)], tables, palettes, DIGIT_FONT, style.edges, style.K,
+                    label_scale=style.label_scale, untracked=style.untracked, **kw)
 
 
-def draw_poses_nv12(surfaces, width, results, scale_factor=None, style=None, matrix='bt601', full_range=False):
+def draw_poses_nv12(surfaces, width, results, scale_factor=None, style=None, matrix='bt601', full_range=False,
+                    ids=None):
     """Draws `results` into NV12 `surfaces` in place and returns `surfaces`.  surfaces: one [H0 * 3 // 2, pitch] uint8
     device tensor or a list of them, of any sizes; `width`, `matrix`, `full_range` and `scale_factor` one value or one
     per surface, as in ``preprocess_surfaces_nv12``.  results, per surface: the (bboxes, labels, kpts) device tuple
     ``push()`` and ``infer_video`` yield, or dict(bboxes=, kpts=, keep=) with fixed shapes.  scale_factor: None for
     results made with rescale=True, else the img_meta's scale_factor (its first two entries divide x and y).  More
-    than 32 surfaces go in several launches."""
+    than 32 surfaces go in several launches.  ids: the int32 [N] device tensor ``PoseTracker.update`` returned for
+    the surface's result (a list for a list of surfaces, None where a surface has none): poses are coloured and
+    labelled by id as `style`, a ``TrackStyle``, says.  An NV12 chroma sample under a digit takes the ink's U, V for
+    its whole 2 x 2 block."""
     who = 'draw_poses_nv12'
-    surf, poses, style = _gather(surfaces, results, style, who)
+    surf, poses, style, ids = _gather(surfaces, results, style, who, ids)
     n = len(surf)
     widths = _per_surface(width, n, 'width', (int, np.integer), who)
     modes = list(zip(_per_surface(matrix, n, 'matrix', str, who),
@@ -232,18 +311,18 @@ def draw_poses_nv12(surfaces, width, results, scale_factor=None, style=None, mat
     tables = [style.table_bytes(m, f) for m, f in combos]
     items = [(s, w, kp, bb, keep, sc, combos.index(md))
              for s, w, (kp, bb, keep), sc, md in zip(surf, widths, poses, scales, modes)]
-    _draw('nv12', items, tables, style)
+    _draw('nv12', items, tables, style, ids, None if ids is None else [style.palette_bytes(m, f) for m, f in combos])
     return surfaces
 
 
-def draw_poses_bgr(images, results, scale_factor=None, style=None):
+def draw_poses_bgr(images, results, scale_factor=None, style=None, ids=None):
     """Draws `results` into [H, W, 3] uint8 BGR device `images` (one tensor or a list, any sizes) in place and returns
-    `images`; results, scale_factor and style as in ``draw_poses_nv12``."""
+    `images`; results, scale_factor, style and ids as in ``draw_poses_nv12``."""
     who = 'draw_poses_bgr'
-    surf, poses, style = _gather(images, results, style, who)
+    surf, poses, style, ids = _gather(images, results, style, who, ids)
     scales = _scales(scale_factor, len(surf), who)
     items = [(s, None, kp, bb, keep, sc, 0) for s, (kp, bb, keep), sc in zip(surf, poses, scales)]
-    _draw('bgr', items, [style.table_bytes()], style)
+    _draw('bgr', items, [style.table_bytes()], style, ids, None if ids is None else [style.palette_bytes()])
     return images
 
 

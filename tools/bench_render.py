@@ -2,7 +2,9 @@
 surfaces, HIP events, warm-up, medians; beside each draw time two references on the same surfaces:
   (a) a device-to-device copy of the surfaces: the floor of touching every byte (the draw writes covered bytes only);
   (b) the pinned device -> host -> device round trip of the surfaces: the least a host renderer pays before it draws.
-The poses are seeded figures of ~400 px spread over the picture, thickness = radius = 4, boxes on.
+The poses are seeded figures of ~400 px spread over the picture, thickness = radius = 4, boxes on.  Beside every
+plain draw, in the same run, the draw with track ids (pose p has id p + 1: a colour per id and a label at
+label_scale 2 on every pose), on the same surfaces and poses.
 python tools/bench_render.py [reps=50] [out=profiles/render_bench.txt]"""
 import os
 import statistics
@@ -11,7 +13,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pavenet_amd.render import PoseStyle, draw_poses_nv12  # noqa: E402
+from pavenet_amd.render import PoseStyle, TrackStyle, draw_poses_nv12  # noqa: E402
 
 W, H, PITCH = 1920, 1080, 2048
 
@@ -46,6 +48,7 @@ def main():
     out = sys.argv[2] if len(sys.argv) > 2 else None
     assert torch.cuda.is_available(), 'bench_render needs an MI355X'
     style = PoseStyle(17, thickness=4, radius=4, draw_boxes=True)
+    track_style = TrackStyle(17, thickness=4, radius=4, draw_boxes=True, label_scale=2)
     lines = [f'draw_poses_nv12, {W} x {H} NV12 (pitch {PITCH}, {H * 3 // 2 * PITCH / 1e6:.2f} MB per surface), K = 17, '
              f'thickness = radius = 4, boxes on; median (min .. max) of {reps} event-timed calls, ms',
              f'{torch.cuda.get_device_name(0)}']
@@ -73,6 +76,11 @@ def main():
             verdict = 'slower than (b)' if t[0] > b[0] else f'{b[0] / t[0]:.1f} x faster than (b)'
             lines.append(f'  N = {n:3d} poses per surface: draw {t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})  [{verdict}; '
                          f'{t[0] / a[0]:.2f} x (a)]')
+            ids = [torch.arange(1, n + 1, dtype=torch.int32).cuda() for _ in range(n_surf)]
+            ids = ids[0] if n_surf == 1 else ids
+            u = _median_ms(lambda: draw_poses_nv12(arg[0], W, arg[1], style=track_style, ids=ids), reps)
+            lines.append(f'                            with ids and labels (g = 2) {u[0]:.3f} ({u[1]:.3f} .. {u[2]:.3f})  '
+                         f'[{u[0] / t[0]:.2f} x the plain draw]')
     text = '\n'.join(lines)
     print(text)
     if out:
