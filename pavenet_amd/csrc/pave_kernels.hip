@@ -240,6 +240,7 @@ struct FusedParams {
   int P;  // points per level (GRID: 4; POSE: K)
   int ref_L;  // level rows behind every reference entry: L, or 1 = one row shared by the L levels
   int n_slabs;  // frame slabs behind `value`: every slab index is clamped into [0, n_slabs)
+  int n_table;  // entries of `frame_table` (n_clips * T): every index into it is clamped into [0, n_table)
   int proj_stride;
   int n_blocks_logical;
 };
@@ -270,6 +271,15 @@ __device__ __forceinline__ int xcd_remap(int b, int nb) {
   const int per = nb >> 3, rem = nb & 7;
   const int x = b & 7, idx = b >> 3;
   return x * per + min(x, rem) + idx;
+}
+
+// Slab of `value` that a unit of clip `clip` samples in frame t: through the frame table when there is one,
+// and clamped -- a frame table / unit_clip entry outside its range reads a wrong slab, never memory outside
+// the table or the value tensor.  Every fused kernel resolves its slab here.
+__device__ __forceinline__ int fused_slab(const FusedParams& p, int clip, int t) {
+  int s = clip * p.T + t;
+  if (p.frame_table) s = p.frame_table[min(max(s, 0), p.n_table - 1)];
+  return min(max(s, 0), p.n_slabs - 1);
 }
 
 template <int MODE, int PPL, int WQ>
@@ -346,9 +356,7 @@ __global__ __launch_bounds__(256) void fused_deform_attn_kernel(const FusedParam
     const int lp0 = (MODE == kGrid) ? 0 : lvl * P;
     const float* lg = logit_row + (t * kHeads + h) * LP + lp0;
     const float* of = off_row + ((long long)(t * kHeads + h) * LP + lp0) * 2;
-    // (clamped: a frame table / unit_clip entry outside the value tensor reads a wrong slab, never
-    // memory outside it)
-    const int slab = min(max(p.frame_table ? p.frame_table[clip * T + t] : clip * T + t, 0), p.n_slabs - 1);
+    const int slab = fused_slab(p, clip, t);
     const char* frame = reinterpret_cast<const char*>(p.value) +
                         (long long)slab * p.S * rowbytes + j * 16;
 
@@ -846,7 +854,7 @@ __global__ __launch_bounds__(256) void enc_head_major_kernel(const FusedParams p
     const float inv_sum = 1.f / sm;
     const int clip = p.unit_clip ? p.unit_clip[unit] : unit / p.units_per_clip;
     const char* frame =
-        reinterpret_cast<const char*>(p.value) + (long long)clip * p.S * rowbytes + j * 16;
+        reinterpret_cast<const char*>(p.value) + (long long)fused_slab(p, clip, 0) * p.S * rowbytes + j * 16;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       Corners c;
@@ -1706,6 +1714,7 @@ FusedParams fused_params(const float* value, const int64_t* spatial_shapes, cons
   p.value = value, p.shapes = spatial_shapes, p.lsi = level_start, p.proj = proj, p.ref = ref;
   p.frame_table = frame_table;
   p.n_slabs = frame_table ? n_slabs : n_clips * T;
+  p.n_table = n_clips * T;
   p.out = out, p.stat_max = stat_max, p.stat_sum = stat_sum;
   p.T = T, p.S = S, p.L = L, p.ref_L = ref_levels, p.proj_stride = proj_stride;
   return p;

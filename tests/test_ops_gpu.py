@@ -275,6 +275,22 @@ def test_frame_table_entries_outside_the_value_cache_cannot_fault():
     b = deform_attn_grid_fused(value, sd, ld, proj, ref, frame_table=ok, **kw)
     torch.cuda.synchronize()
     assert torch.equal(a, b)
+    # T = 1: the head-major kernel (dense rows) and the per-query kernel (a row stride that is no multiple of 4
+    # floats) resolve the slab in the same way, for far-out entries of the frame table and of unit_clip
+    proj1 = proj[:, :384].contiguous()
+    uc = (torch.arange(U, dtype=torch.int32) % 3).cuda()
+    far_uc = torch.tensor([1, 2 ** 30, -7, 0, 2, -2 ** 31, 2 ** 31 - 1, 1], dtype=torch.int32).cuda()
+    kw1 = dict(T=1, n_clips=3, units_per_clip=U)
+    for rows in (proj1, torch.cat([proj1, proj1[:, :1]], 1)):
+        assert (rows.stride(0) % 4 == 0) == (rows is proj1)
+        a = deform_attn_grid_fused(value, sd, ld, rows, ref[:1], frame_table=bad, unit_clip=uc, **kw1)
+        b = deform_attn_grid_fused(value, sd, ld, rows, ref[:1], frame_table=ok, unit_clip=uc, **kw1)
+        c = deform_attn_grid_fused(value, sd, ld, rows, ref[:1], frame_table=ok, unit_clip=far_uc, **kw1)
+        d = deform_attn_grid_fused(value, sd, ld, rows, ref[:1], frame_table=ok, unit_clip=far_uc.clamp(0, 2), **kw1)
+        e = deform_attn_grid_fused(value[:3], sd, ld, rows, ref[:1], unit_clip=far_uc, **kw1)
+        f = deform_attn_grid_fused(value[:3], sd, ld, rows, ref[:1], unit_clip=far_uc.clamp(0, 2), **kw1)
+        torch.cuda.synchronize()
+        assert torch.equal(a, b) and torch.equal(c, d) and torch.equal(e, f)
     K = 15
     pproj = _t(seeded_array('ft.pproj', (U, T * 8 * 4 * K * 3))).cuda()
     pref = (_t(seeded_array('ft.pref', (1, T * U, 4, 2 * K), 0.2)) + 0.5).cuda()
