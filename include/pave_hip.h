@@ -484,6 +484,54 @@ int pave_draw_tracks_nv12(const pave_draw_ids_plan* plan, void* stream);
 int pave_draw_tracks_bgr(const pave_draw_ids_plan* plan, void* stream);
 
 /*
+ * People hidden in surfaces on the device (pavenet_amd/csrc/pave_anon.hip; the rule is DESIGN section 15,
+ * integer-exact), one launch for n separately allocated surfaces of any sizes, in place.  The plan is copied into the
+ * kernel's arguments.
+ *   dst, kpts, bboxes, keep, pitch, width, height, n_poses, scale, table: as in pave_draw_plan, with the same
+ *              quantisation and the same rule for which poses count and which key points are visible
+ *   fill[t]    the 3 bytes mode 1 stores, as they are: (Y, U, V) for _nv12, (B, G, R) for _bgr
+ *   head[h]    the n_head key points of the head
+ *   region     0: the head (the bounding rectangle A of the visible head key points, e its larger side, grown by
+ *              r = 4 margin + max((e head_scale) >> 4, (s head_min) >> 4) quarter pixels, s the larger side of the
+ *              quantised box); 1: the person (A the box, r = 4 margin + ((s grow) >> 4))
+ *   fallback_skip  a pose without a visible head key point under region 0 takes its person region (0) or none (1)
+ *   cell       the picture is cut into cell x cell pixel cells from its origin; a cell is masked iff a region's A is
+ *              within r of the rectangle of its pixels' points
+ *   mode       0: every sample of a plane in a masked cell becomes (2 sum + n) / (2 n) over the cell's n original
+ *              samples of that plane (NV12: Y over the pixels, U and V over the chroma samples; BGR: per channel);
+ *              1: it becomes the fill colour
+ * Only the bytes of masked cells are written.
+ * Refused with PAVE_E_ARG before any device call: a null plan, surface or pose tensor (n_poses > 0), n outside
+ * 1 .. 32, width or height outside 1 .. 8192, odd NV12 sizes, a pitch below a row's bytes, n_poses outside 0 .. 4096,
+ * K outside 1 .. 32, n_head outside 0 .. 8 (0 with region 0), a head index >= K, a cell that is not 2, 4, 8, 16, 32 or
+ * 64, margin outside 0 .. 64, grow, head_scale or head_min outside 0 .. 32, region, mode or fallback_skip outside
+ * {0, 1}, a scale that is not positive and finite, a table index >= 4.  A plan that passes cannot address memory
+ * outside its tensors, whatever the pose values are.
+ */
+#define PAVE_ANON_MAX_HEAD 8
+#define PAVE_ANON_MAX_CELL 64
+#define PAVE_ANON_MAX_MARGIN 64
+#define PAVE_ANON_MAX_SIXTEENTHS 32
+typedef struct pave_anon_plan {
+  void*          dst[PAVE_DRAW_MAX_SURFACES];
+  const float*   kpts[PAVE_DRAW_MAX_SURFACES];
+  const float*   bboxes[PAVE_DRAW_MAX_SURFACES];
+  const int32_t* keep[PAVE_DRAW_MAX_SURFACES];
+  int            pitch[PAVE_DRAW_MAX_SURFACES];
+  int            width[PAVE_DRAW_MAX_SURFACES];
+  int            height[PAVE_DRAW_MAX_SURFACES];
+  int            n_poses[PAVE_DRAW_MAX_SURFACES];
+  float          scale[PAVE_DRAW_MAX_SURFACES][2];
+  uint8_t        table[PAVE_DRAW_MAX_SURFACES];
+  uint8_t        fill[PAVE_DRAW_MAX_TABLES][3];
+  uint8_t        head[PAVE_ANON_MAX_HEAD];
+  int n, K, n_head, region, mode, fallback_skip, cell, margin, grow, head_scale, head_min;
+  float score_thr, kpt_thr;
+} pave_anon_plan;
+int pave_anonymize_nv12(const pave_anon_plan* plan, void* stream);
+int pave_anonymize_bgr(const pave_anon_plan* plan, void* stream);
+
+/*
  * Track ids: the poses of a frame linked to the poses of the frames before it (pavenet_amd/csrc/pave_track.hip; the
  * rule is DESIGN section 14, integer-exact), one launch for `entries` frames of any of `cameras` cameras.  The plan
  * is copied into the kernel's arguments.  One block per camera of the launch takes that camera's entries in plan

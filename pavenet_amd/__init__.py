@@ -35,6 +35,9 @@ def __getattr__(name):
     if name in ('PoseStyle', 'TrackStyle', 'draw_poses_nv12', 'draw_poses_bgr', 'bgr_to_yuv'):
         from . import render
         return getattr(render, name)
+    if name in ('PrivacyStyle', 'anonymize_nv12', 'anonymize_bgr'):
+        from . import anonymize
+        return getattr(anonymize, name)
     if name == 'PoseTracker':
         from . import tracking
         return tracking.PoseTracker

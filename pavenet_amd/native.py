@@ -139,7 +139,25 @@ class DrawIdsPlan(ctypes.Structure):
                 ('font', (ctypes.c_uint8 * 7) * 10), ('label_scale', ctypes.c_int), ('untracked_skip', ctypes.c_int)]
 
 
-TRACK_MAX_FRAMES, TRACK_MAX_POSES, TRACK_MAX_TRACKS, TRACK_MAX_K, TRACK_MAX_CAMERAS = (
+ANON_MAX_HEAD, ANON_MAX_CELL, ANON_MAX_MARGIN, ANON_MAX_SIXTEENTHS = (
+    DEFINES['PAVE_ANON_MAX_' + n] for n in ('HEAD', 'CELL', 'MARGIN', 'SIXTEENTHS'))
+
+
+class AnonPlan(ctypes.Structure):
+    """`pave_anon_plan` of include/pave_hip.h (the by-value argument of pave_anonymize_nv12 / _bgr)."""
+    _fields_ = [('dst', ctypes.c_void_p * DRAW_MAX_SURFACES), ('kpts', ctypes.c_void_p * DRAW_MAX_SURFACES),
+                ('bboxes', ctypes.c_void_p * DRAW_MAX_SURFACES), ('keep', ctypes.c_void_p * DRAW_MAX_SURFACES),
+                ('pitch', ctypes.c_int * DRAW_MAX_SURFACES), ('width', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('height', ctypes.c_int * DRAW_MAX_SURFACES), ('n_poses', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('scale', (ctypes.c_float * 2) * DRAW_MAX_SURFACES), ('table', ctypes.c_uint8 * DRAW_MAX_SURFACES),
+                ('fill', (ctypes.c_uint8 * 3) * DRAW_MAX_TABLES), ('head', ctypes.c_uint8 * ANON_MAX_HEAD),
+                ('n', ctypes.c_int), ('K', ctypes.c_int), ('n_head', ctypes.c_int), ('region', ctypes.c_int),
+                ('mode', ctypes.c_int), ('fallback_skip', ctypes.c_int), ('cell', ctypes.c_int),
+                ('margin', ctypes.c_int), ('grow', ctypes.c_int), ('head_scale', ctypes.c_int),
+                ('head_min', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
+
+
+TRACK_MAX_FRAMES, TRACK_MAX_POSES,TRACK_MAX_TRACKS, TRACK_MAX_K, TRACK_MAX_CAMERAS = (
     DEFINES['PAVE_TRACK_MAX_' + n] for n in ('FRAMES', 'POSES', 'TRACKS', 'K', 'CAMERAS'))
 
 

@@ -550,6 +550,12 @@ def _draw_shapes(who, kind, items, colors, edges, K, thickness, radius):
         colors = []
     if not 1 <= len(colors) <= native.DRAW_MAX_TABLES or any(len(tab) != 3 * native.DRAW_COLORS for tab in colors):
         raise ValueError(f'{who}: colors are 1 .. {native.DRAW_MAX_TABLES} tables of {native.DRAW_COLORS} x 3 bytes')
+    return items, edges, K, _surface_geometry(who, kind, items, K, len(colors)), b''.join(colors)   # [tables][65][3]
+
+
+def _surface_geometry(who, kind, items, K, tables, table_name='colour table'):
+    """The checks of an item's first seven entries (surface, width, kpts, bboxes, keep, (sx, sy), table), all
+    ValueError -> [(pitch, W, H, N, sx, sy, table)]."""
     if not items:
         raise ValueError(f'{who}: no surface')
     geometry = []
@@ -589,10 +595,10 @@ def _draw_shapes(who, kind, items, colors, edges, K, thickness, radius):
         sx, sy = (float(v) for v in scale)
         if not (0 < sx < float('inf') and 0 < sy < float('inf')):
             raise ValueError(f'{who}: the scale of surface {i} must be positive and finite, got {(sx, sy)}')
-        if not 0 <= int(table) < len(colors):
-            raise ValueError(f'{who}: surface {i} names colour table {table} of {len(colors)}')
+        if not 0 <= int(table) < tables:
+            raise ValueError(f'{who}: surface {i} names {table_name} {table} of {tables}')
         geometry.append((int(pitch), int(W), int(H), N, sx, sy, int(table)))
-    return items, edges, K, geometry, b''.join(colors)   # [tables][65][3], the plan's layout
+    return geometry
 
 
 def _draw_device(who, items):
@@ -701,7 +707,71 @@ def draw_tracks(kind, items, colors, palettes, font, edges, K, *, label_scale=2,
         _launch(entry, who, dev, ctypes.byref(plan))
 
 
-_TRACK_STATE = (('id', 1), ('last', 1), ('kpts', 2), ('vis', 1), ('area', 1), ('frame', 0), ('next_id', 0),
+ANON_CELLS = (2, 4, 8, 16, 32, 64)
+
+
+def anonymize(kind, items, fills, head, K, *, region='head', mode='pixelate', cell=16, margin=0, grow=2, head_scale=12,
+              head_min=2, fallback='person', score_thr=0.3, kpt_thr=0.):
+    """People hidden in surfaces in place, one launch per 32 surfaces (pave_anonymize_nv12 / _bgr; the rule is DESIGN
+    section 15).  kind and items: as in draw_poses, an item's table naming one of `fills`: 1 .. 4 triples of bytes
+    stored as they are by mode 'fill'.  head: up to 8 key-point indices < K (needed by region 'head').  region 'head' |
+    'person', mode 'pixelate' | 'fill', cell one of 2, 4, 8, 16, 32, 64 pixels, margin 0 .. 64 pixels, grow, head_scale
+    and head_min 0 .. 32 sixteenths, fallback 'person' | 'skip'.  Shapes, types and ranges raise ValueError before
+    anything is asked of a device."""
+    who = 'anonymize'
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
+    items, K = list(items), int(K)
+    if not 1 <= K <= native.DRAW_MAX_K:
+        raise ValueError(f'{who}: K in 1 .. {native.DRAW_MAX_K}, got {K}')
+    for value, name, allowed in ((region, 'region', ('head', 'person')), (mode, 'mode', ('pixelate', 'fill')),
+                                 (fallback, 'fallback', ('person', 'skip')), (cell, 'cell', ANON_CELLS)):
+        if isinstance(value, bool) or value not in allowed:
+            raise ValueError(f'{who}: {name} is one of {allowed}, got {value!r}')
+    for value, name, top in ((margin, 'margin', native.ANON_MAX_MARGIN), (grow, 'grow', native.ANON_MAX_SIXTEENTHS),
+                             (head_scale, 'head_scale', native.ANON_MAX_SIXTEENTHS),
+                             (head_min, 'head_min', native.ANON_MAX_SIXTEENTHS)):
+        if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= top:
+            raise ValueError(f'{who}: {name} is an integer in 0 .. {top}, got {value!r}')
+    try:
+        head = [int(k) for k in head]
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: head is a list of key-point indices') from None
+    if len(head) > native.ANON_MAX_HEAD or any(not 0 <= k < K for k in head):
+        raise ValueError(f'{who}: head is at most {native.ANON_MAX_HEAD} indices in [0, {K}), got {head}')
+    if region == 'head' and not head:
+        raise ValueError(f"{who}: region 'head' needs head indices")
+    try:
+        fills = [bytes(int(c) for c in f) for f in fills]
+    except (TypeError, ValueError):
+        fills = []
+    if not 1 <= len(fills) <= native.DRAW_MAX_TABLES or any(len(f) != 3 for f in fills):
+        raise ValueError(f'{who}: fills are 1 .. {native.DRAW_MAX_TABLES} triples of bytes')
+    geometry = _surface_geometry(who, kind, items, K, len(fills), 'fill')
+    dev = _draw_device(who, items)
+    entry = 'pave_anonymize_nv12' if kind == 'nv12' else 'pave_anonymize_bgr'
+    raw_fills = b''.join(fills)
+    for at in range(0, len(items), native.DRAW_MAX_SURFACES):
+        plan = native.AnonPlan()
+        part = items[at:at + native.DRAW_MAX_SURFACES]
+        for i, it in enumerate(part):
+            pitch, W, H, N, sx, sy, table = geometry[at + i]
+            plan.dst[i], plan.kpts[i], plan.bboxes[i], plan.keep[i] = it[0].data_ptr(), it[2].data_ptr(), \
+                it[3].data_ptr(), _ptr(it[4])
+            plan.pitch[i], plan.width[i], plan.height[i], plan.n_poses[i] = pitch, W, H, N
+            plan.scale[i][0], plan.scale[i][1], plan.table[i] = sx, sy, table
+        ctypes.memmove(plan.fill, raw_fills, len(raw_fills))
+        for h, k in enumerate(head):
+            plan.head[h] = k
+        plan.n, plan.K, plan.n_head = len(part), K, len(head)
+        plan.region, plan.mode = int(region == 'person'), int(mode == 'fill')
+        plan.fallback_skip, plan.cell, plan.margin, plan.grow = int(fallback == 'skip'), int(cell), int(margin), int(grow)
+        plan.head_scale, plan.head_min = int(head_scale), int(head_min)
+        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        _launch(entry, who, dev, ctypes.byref(plan))
+
+
+_TRACK_STATE =(('id', 1), ('last', 1), ('kpts', 2), ('vis', 1), ('area', 1), ('frame', 0), ('next_id', 0),
                 ('dropped', 0))   # name, kind: 0 [cameras], 1 [cameras, M], 2 [cameras, M, K, 2]
 
 

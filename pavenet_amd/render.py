@@ -248,8 +248,8 @@ def _poses(result, i, who):
     return kpts.contiguous(), bboxes.contiguous(), None if keep is None else keep.contiguous()
 
 
-def _gather(surfaces, results, style, who, ids=None):
-    """-> (surfaces, poses, style, ids): lists of one entry per surface; ids None when the call has none."""
+def _surfaces_and_poses(surfaces, results, who):
+    """One tensor and its result, or lists of them -> (single, surfaces, poses): lists of one entry per surface."""
     single = isinstance(surfaces, torch.Tensor)
     surf = [surfaces] if single else (list(surfaces) if isinstance(surfaces, (list, tuple)) else None)
     if not surf:
@@ -257,7 +257,12 @@ def _gather(surfaces, results, style, who, ids=None):
     results = [results] if single else (list(results) if isinstance(results, (list, tuple)) else None)
     if results is None or len(results) != len(surf):
         raise ValueError(f'{who}: one result per surface ({len(surf)})')
-    poses = [_poses(r, i, who) for i, r in enumerate(results)]
+    return single, surf, [_poses(r, i, who) for i, r in enumerate(results)]
+
+
+def _gather(surfaces, results, style, who, ids=None):
+    """-> (surfaces, poses, style, ids): lists of one entry per surface; ids None when the call has none."""
+    single, surf, poses = _surfaces_and_poses(surfaces, results, who)
     K = poses[0][0].shape[1]
     if ids is not None:
         ids = [ids] if single and isinstance(ids, torch.Tensor) else (list(ids) if isinstance(ids, (list, tuple)) else None)
