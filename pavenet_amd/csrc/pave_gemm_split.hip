@@ -9,7 +9,10 @@
 //     a*b = a0b0 + (a0b1 + a1b0) + (a0b2 + a1b1 + a2b0) + [a1b2 + a2b1 + a2b2]
 // where the bracket is <= 2^-23 |ab| -- below fp32's own rounding of the product sum.  Six bf16
 // MFMAs therefore give a GEMM with fp32-level accuracy (tests/test_ops_gpu.py measures it
-// against fp64 next to the native fp32 MFMA) at 2.5 PF / 6 = 417 TFLOP/s peak, 2.7x the fp32
+// against fp64 next to the native fp32 MFMA; the anchor is tests/test_gemm_exact_gpu.py: on
+// integer operands whose partial sums stay below 2^24 and whose bracket is identically zero
+// every form of this file and of pave_gemm_dma.hip -- whatever its summation order -- must give
+// the bits of the int64 result) at 2.5 PF / 6 = 417 TFLOP/s peak, 2.7x the fp32
 // MFMA rate.  Weights are split once on the host side (pave_split_bf16x3_f32); activations are
 // split while they are staged into LDS, so HBM traffic is that of an fp32 GEMM.
 //
