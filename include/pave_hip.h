@@ -581,6 +581,33 @@ typedef struct pave_track_plan {
 int pave_track_poses(const pave_track_plan* plan, void* stream);
 
 /*
+ * Track ids with a constant-velocity motion model (the same kernel source; DESIGN section 14, "Motion"): a slot is
+ * compared where it is predicted to be, not where it was, and keeps a velocity that every match refreshes.
+ *   base         everything of pave_track_plan, with the same meaning and the same refusals
+ *   track_vel    DEVICE [cameras, M, 2] int32, read and written: (vx, vy) in 1/16 quarter pixel per frame
+ *   track_hits   DEVICE [cameras, M] int32, read and written: the matches of the slot's track, its birth included
+ *                (1: no velocity measured yet), saturating at 32767.  Neither is read in a free slot
+ *   gain         1 .. 16, sixteenths: the weight of the newest measured velocity
+ *   max_predict  0 .. 255: the most frames a slot is extrapolated over
+ *   new_gate     1 .. 16: the factor on C[k] in the agreement test of a slot with hits == 1
+ * With gap = frame - last and g = min(gap, max_predict) a live slot's point is P = clamp(kpts + ((vel g + 8) >> 4), 0,
+ * 32767) and takes the place of kpts in the pair score; a match measures m = floor((32 S + n gap) / (2 n gap)), S the
+ * sum of (detection - stored point) over the n key points visible in both, and stores vel = m when hits == 1, else
+ * clamp((gain m + (16 - gain) vel + 8) >> 4, -32768, 32767); a birth stores vel = 0, hits = 1.
+ * Refused with PAVE_E_ARG before any device call: whatever pave_track_poses refuses in base, a null track_vel or
+ * track_hits, gain outside 1 .. 16, max_predict outside 0 .. 255, new_gate outside 1 .. 16.  Predictions are
+ * clamped by the rule and velocities by their stores: a plan that passes cannot address memory outside its tensors,
+ * whatever the pose values and the stored velocities are.
+ */
+typedef struct pave_track_motion_plan {
+  pave_track_plan base;
+  int32_t* track_vel;
+  int32_t* track_hits;
+  int gain, max_predict, new_gate;
+} pave_track_motion_plan;
+int pave_track_poses_motion(const pave_track_motion_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

@@ -21,6 +21,12 @@
 // ballot) are reduced again, one wave per row.  Births are a serial scan by one lane; the stores are made by all.
 // Every loop bound is from the plan, the exit of the greedy loop and every barrier are block-uniform, there are no
 // global atomics and nothing waits on memory.
+//
+// With the motion model (pave_track_poses_motion; DESIGN section 14, "Motion") the same kernel, MOTION = true: a live
+// slot goes into LDS where it is predicted to be, kpts + ((vel min(gap, max_predict) + 8) >> 4) clamped, with the
+// factor of its agreement test beside it (new_gate while hits == 1), and after the greedy rounds thread t measures
+// the velocity of matched slot t from the points the slot still holds in global memory -- a phase of its own, behind
+// a barrier and two barriers before the stores that overwrite those points.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -58,7 +64,26 @@ __device__ __forceinline__ u64 wave_max(u64 v) {
   return v;
 }
 
-__global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan plan) {
+// floor(a / b) for b > 0 (C's / truncates)
+__device__ __forceinline__ long long floor_div(const long long a, const long long b) {
+  const long long q = a / b;
+  return q - ((a % b) < 0 ? 1 : 0);
+}
+
+template <bool MOTION>
+struct track_arg {
+  typedef pave_track_plan type;
+};
+template <>
+struct track_arg<true> {
+  typedef pave_track_motion_plan type;
+};
+__device__ __forceinline__ const pave_track_plan& base_of(const pave_track_plan& p) { return p; }
+__device__ __forceinline__ const pave_track_plan& base_of(const pave_track_motion_plan& p) { return p.base; }
+
+template <bool MOTION>
+__global__ __launch_bounds__(NT) void track_poses_kernel(const typename track_arg<MOTION>::type arg) {
+  const pave_track_plan& plan = base_of(arg);
   __shared__ unsigned int det_xy[MAXP * ROW], trk_xy[MAXT * ROW];
   __shared__ unsigned int det_vis[MAXP], trk_vis[MAXT];
   __shared__ int det_area[MAXP], trk_area[MAXT];
@@ -69,6 +94,8 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
   __shared__ u64 row_best[MAXP];     // the largest key of the row among the slots not yet taken
   __shared__ u64 wave_best[WAVES], lost_rows[WAVES];
   __shared__ int cam_state[3];       // frame, next_id, dropped
+  // MOTION: the predicted shift of a live slot (quarter pixels, within +-32767) and the factor on C[k] of its test
+  __shared__ int trk_shift[MOTION ? MAXT : 1][2], trk_gate[MOTION ? MAXT : 1];
 
   const int b = blockIdx.x;
   const int cam = plan.camera[b];
@@ -82,6 +109,12 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
   uint32_t* __restrict__ g_vis = plan.track_vis + (long long)cam * M;
   int32_t* __restrict__ g_area = plan.track_area + (long long)cam * M;
   u64* __restrict__ keys = reinterpret_cast<u64*>(plan.scratch) + (long long)b * MAXP * MAXT;
+  int32_t* __restrict__ g_vel = nullptr;
+  int32_t* __restrict__ g_hits = nullptr;
+  if constexpr (MOTION) {
+    g_vel = arg.track_vel + (long long)cam * M * 2;
+    g_hits = arg.track_hits + (long long)cam * M;
+  }
 
   if (tid == 0) {
     cam_state[0] = plan.frame[cam];
@@ -98,6 +131,7 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
     const float* __restrict__ bboxes = plan.bboxes[e];
     const int32_t* __restrict__ keep = plan.keep[e];
     const int frame = cam_state[0] + 1;
+    int my_gap = 1, my_hits = 1, my_vx = 0, my_vy = 0;   // MOTION: slot tid as the frame before left it
 
     // ---- 1, 2: expire the slots; the detections' validity and area ----
     if (tid < M) {
@@ -110,6 +144,21 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
       trk_det[tid] = -1;
       trk_vis[tid] = g_vis[tid];
       trk_area[tid] = g_area[tid];
+      if constexpr (MOTION) {
+        if (id != 0) {
+          // ---- 3b: where the slot is predicted to be ----
+          my_gap = frame - g_last[tid];
+          my_hits = g_hits[tid];
+          my_vx = g_vel[2 * tid];
+          my_vy = g_vel[2 * tid + 1];
+          const long long g = min(my_gap, arg.max_predict);
+          const long long shx = ((long long)my_vx * g + 8) >> 4, shy = ((long long)my_vy * g + 8) >> 4;
+          // (a stored point is within 0 .. 32767: a shift beyond +-32767 clamps to the same end)
+          trk_shift[tid][0] = (int)min(max(shx, (long long)-QMAX), (long long)QMAX);
+          trk_shift[tid][1] = (int)min(max(shy, (long long)-QMAX), (long long)QMAX);
+          trk_gate[tid] = my_hits == 1 ? arg.new_gate : 1;
+        }
+      }
     }
     if (tid < n) {
       const float* bb = bboxes + tid * 5;
@@ -134,8 +183,15 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
     }
     for (int i = tid; i < M * K; i += NT) {
       const int t = i / K, k = i - t * K;
-      if (trk_id[t] != 0)
-        trk_xy[t * ROW + k] = ((unsigned)g_kpts[2 * i] & QMAX) | (((unsigned)g_kpts[2 * i + 1] & QMAX) << 16);
+      if (trk_id[t] != 0) {
+        if constexpr (MOTION) {
+          const int px = min(max((int)((unsigned)g_kpts[2 * i] & QMAX) + trk_shift[t][0], 0), QMAX);
+          const int py = min(max((int)((unsigned)g_kpts[2 * i + 1] & QMAX) + trk_shift[t][1], 0), QMAX);
+          trk_xy[t * ROW + k] = (unsigned)px | ((unsigned)py << 16);
+        } else {
+          trk_xy[t * ROW + k] = ((unsigned)g_kpts[2 * i] & QMAX) | (((unsigned)g_kpts[2 * i + 1] & QMAX) << 16);
+        }
+      }
     }
     __syncthreads();
 
@@ -145,7 +201,8 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
       u64 key = 0;
       if (det_bad[d] == 0 && trk_id[t] != 0) {
         const unsigned both = det_vis[d] & trk_vis[t];
-        const long long area = (long long)det_area[d] + (long long)trk_area[t];
+        long long area = (long long)det_area[d] + (long long)trk_area[t];
+        if constexpr (MOTION) area *= trk_gate[t];   // (C[k] G (area_d + area_t) < 2^24 16 2^31)
         int s = 0;
         long long D = 0;
         for (int k = 0; k < K; ++k) {
@@ -210,6 +267,36 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
     }
     __syncthreads();
 
+    // ---- 6': the velocity of a matched slot, from the points it still holds (the stores below overwrite them) ----
+    bool matched = false;
+    if constexpr (MOTION) {
+      const int d = tid < M ? trk_det[tid] : -1;   // (no birth yet: >= 0 is a match of step 5)
+      if (d >= 0) {
+        matched = true;
+        const unsigned cov = det_vis[d] & trk_vis[tid];
+        const long long cnt = __popc(cov);
+        long long Sx = 0, Sy = 0;
+        for (int k = 0; k < K; ++k) {
+          if (cov >> k & 1u) {
+            const unsigned a = det_xy[d * ROW + k];
+            Sx += (int)(a & 0xffffu) - g_kpts[2 * (tid * K + k)];
+            Sy += (int)(a >> 16) - g_kpts[2 * (tid * K + k) + 1];
+          }
+        }
+        const long long ng = cnt * (long long)my_gap;
+        if (ng > 0) {   // (a candidate has n >= min_kpts >= 1 and a live slot gap >= 1)
+          const long long mx = floor_div(32 * Sx + ng, 2 * ng), my = floor_div(32 * Sy + ng, 2 * ng);
+          const long long gn = arg.gain;
+          const long long vx = my_hits == 1 ? mx : (gn * mx + (16 - gn) * (long long)my_vx + 8) >> 4;
+          const long long vy = my_hits == 1 ? my : (gn * my + (16 - gn) * (long long)my_vy + 8) >> 4;
+          my_vx = (int)min(max(vx, -32768ll), 32767ll);
+          my_vy = (int)min(max(vy, -32768ll), 32767ll);
+        }
+        my_hits = my_hits >= 32767 ? 32767 : my_hits + 1;
+      }
+      __syncthreads();   // the births below write trk_det
+    }
+
     // ---- 7: births, in ascending detection index into the lowest free slot ----
     if (tid == 0) {
       int free_t = 0, next_id = cam_state[1], dropped = cam_state[2];
@@ -245,6 +332,11 @@ __global__ __launch_bounds__(NT) void track_poses_kernel(const pave_track_plan p
         g_last[tid] = frame;
         g_vis[tid] = det_vis[d];
         g_area[tid] = det_area[d];
+        if constexpr (MOTION) {   // 7': a birth starts at rest
+          g_vel[2 * tid] = matched ? my_vx : 0;
+          g_vel[2 * tid + 1] = matched ? my_vy : 0;
+          g_hits[tid] = matched ? my_hits : 1;
+        }
       }
     }
     for (int i = tid; i < M * K; i += NT) {
@@ -299,8 +391,23 @@ extern "C" {
 int pave_track_poses(const pave_track_plan* plan, void* stream) {
   const int st = track_check(plan);
   if (st != PAVE_OK) return st;
-  return pave_launch<track_poses_kernel>(dim3((unsigned)plan->entries), dim3(NT), 0,
-                                         reinterpret_cast<hipStream_t>(stream), *plan);
+  return pave_launch<track_poses_kernel<false>>(dim3((unsigned)plan->entries), dim3(NT), 0,
+                                                reinterpret_cast<hipStream_t>(stream), *plan);
+}
+
+int pave_track_poses_motion(const pave_track_motion_plan* plan, void* stream) {
+  if (!plan) return pave_internal_fail(PAVE_E_ARG, "track_poses_motion: null plan");
+  const int st = track_check(&plan->base);
+  if (st != PAVE_OK) return st;
+  if (!plan->track_vel || !plan->track_hits)
+    return pave_internal_fail(PAVE_E_ARG, "track_poses_motion: null velocity or hits tensor");
+  if (plan->gain < 1 || plan->gain > 16) return pave_internal_fail(PAVE_E_ARG, "track_poses_motion: gain outside 1 .. 16");
+  if (plan->max_predict < 0 || plan->max_predict > 255)
+    return pave_internal_fail(PAVE_E_ARG, "track_poses_motion: max_predict outside 0 .. 255");
+  if (plan->new_gate < 1 || plan->new_gate > 16)
+    return pave_internal_fail(PAVE_E_ARG, "track_poses_motion: new_gate outside 1 .. 16");
+  return pave_launch<track_poses_kernel<true>>(dim3((unsigned)plan->base.entries), dim3(NT), 0,
+                                               reinterpret_cast<hipStream_t>(stream), *plan);
 }
 
 }  // extern "C"

@@ -175,6 +175,12 @@ class TrackPlan(ctypes.Structure):
                 ('kpt_thr', ctypes.c_float)]
 
 
+class TrackMotionPlan(ctypes.Structure):
+    """`pave_track_motion_plan` of include/pave_hip.h (the by-value argument of pave_track_poses_motion)."""
+    _fields_ = [('base', TrackPlan), ('track_vel', ctypes.c_void_p), ('track_hits', ctypes.c_void_p),
+                ('gain', ctypes.c_int), ('max_predict', ctypes.c_int), ('new_gate', ctypes.c_int)]
+
+
 _lib = None
 
 

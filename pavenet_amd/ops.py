@@ -781,13 +781,19 @@ def track_scratch(device):
                        device=device)
 
 
-def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0.3, kpt_thr=0.):
+_TRACK_MOTION = ('vel', 'hits', 'gain', 'max_predict', 'new_gate')
+
+
+def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0.3, kpt_thr=0., motion=None):
     """Track ids for frames of poses, one launch per 32 frames (pave_track_poses; the rule is DESIGN section 14).
     entries: one (kpts [N, K, 3] fp32, bboxes [N, 5] fp32, keep [N] int32 or None, camera, (sx, sy)) per frame, N <=
     128, the frames of one camera in time order; state: int32 device tensors id, last, vis, area [cameras, M], kpts
     [cameras, M, K, 2], frame, next_id, dropped [cameras], read and written; scratch: track_scratch(device); C: K
-    pair constants in [1, 2^24).  Returns one int32 [N] tensor of ids per entry.  Shapes, types and ranges raise
-    ValueError before anything is asked of a device."""
+    pair constants in [1, 2^24).  motion: None, or the constant-velocity model of section 14 "Motion"
+    (pave_track_poses_motion) as a dict or a tuple of (vel, hits, gain, max_predict, new_gate): int32 device tensors
+    vel [cameras, M, 2] (1/16 quarter pixel per frame) and hits [cameras, M], read and written, and integers gain
+    1 .. 16, max_predict 0 .. 255, new_gate 1 .. 16.  Returns one int32 [N] tensor of ids per entry.  Shapes, types
+    and ranges raise ValueError before anything is asked of a device."""
     who = 'track_poses'
     entries = list(entries)
     if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name, _ in _TRACK_STATE):
@@ -815,6 +821,21 @@ def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0
         raise ValueError(f'{who}: min_kpts in 1 .. K = {K}, got {min_kpts!r}')
     if int(max_age) != max_age or max_age < 0:
         raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    if motion is not None:
+        if isinstance(motion, dict):
+            if sorted(motion) != sorted(_TRACK_MOTION):
+                raise ValueError(f'{who}: motion holds {", ".join(_TRACK_MOTION)}')
+            motion = tuple(motion[n] for n in _TRACK_MOTION)
+        if not (isinstance(motion, (tuple, list)) and len(motion) == 5):
+            raise ValueError(f'{who}: motion is None or ({", ".join(_TRACK_MOTION)})')
+        vel, hits, gain, max_predict, new_gate = motion
+        for name, t, want in (('vel', vel, (cameras, M, 2)), ('hits', hits, (cameras, M))):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == want
+                    and t.is_contiguous()):
+                raise ValueError(f'{who}: motion {name} must be a contiguous int32 {list(want)} tensor')
+        for name, v, lo, hi in (('gain', gain, 1, 16), ('max_predict', max_predict, 0, 255), ('new_gate', new_gate, 1, 16)):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f'{who}: motion {name} must be an integer in {lo} .. {hi}, got {v!r}')
     checked = []
     for i, entry in enumerate(entries):
         if not (isinstance(entry, (tuple, list)) and len(entry) == 5):
@@ -847,12 +868,15 @@ def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0
         raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
     if any(t.device != dev for t in [state[n] for n, _ in _TRACK_STATE] + [scratch]):
         raise ValueError(f'{who}: the state tensors and the scratch area must be on one device ({dev})')
+    if motion is not None and (vel.device != dev or hits.device != dev):
+        raise ValueError(f'{who}: motion vel and hits must be on the HIP device of the state ({dev})')
     for i, c in enumerate(checked):
         if any(t is not None and t.device != dev for t in c[:3]):
             raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
     ids = [torch.empty((c[6],), dtype=torch.int32, device=dev) for c in checked]
     for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
-        plan = native.TrackPlan()
+        full = native.TrackMotionPlan() if motion is not None else native.TrackPlan()
+        plan = full.base if motion is not None else full
         part = checked[at:at + native.TRACK_MAX_FRAMES]
         for i, (kpts, bboxes, keep, camera, sx, sy, N) in enumerate(part):
             plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
@@ -867,7 +891,10 @@ def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0
         plan.entries, plan.cameras, plan.M, plan.K = len(part), cameras, M, K
         plan.min_kpts, plan.max_age, plan.score_thr, plan.kpt_thr = int(min_kpts), int(max_age), float(score_thr), \
             float(kpt_thr)
-        _launch('pave_track_poses', who, dev, ctypes.byref(plan))
+        if motion is not None:
+            full.track_vel, full.track_hits = vel.data_ptr(), hits.data_ptr()
+            full.gain, full.max_predict, full.new_gate = gain, max_predict, new_gate
+        _launch('pave_track_poses_motion' if motion is not None else 'pave_track_poses', who, dev, ctypes.byref(full))
     return ids
 
 

@@ -4,7 +4,12 @@ takes what ``push()`` / ``infer_video`` yield -- the (bboxes, labels, kpts) devi
 ``dict(bboxes=, kpts=, keep=)`` of ``head.get_bboxes`` -- and returns a device int32 [N] tensor of ids (0 = not
 tracked) without reading a device value on the host.  Ids are per camera, start at 1 and are never reused.
 
-Not built: motion prediction, appearance re-identification, cross-camera identities, optimal assignment.
+With ``motion='constant_velocity'`` (section 14, "Motion") a track also keeps a velocity, measured at every match
+and smoothed, and a pose is compared with where the track is predicted to be, so links survive fast walks, gaps
+and crossings.  The default, ``motion=None``, is the plain rule.
+
+Not built: Kalman filtering, per-key-point velocities, appearance re-identification, cross-camera identities,
+optimal assignment.
 """
 import math
 
@@ -45,10 +50,17 @@ class PoseTracker:
     `score_thr` (and keep, and finite coordinates), a key point counts iff its score is > `kpt_thr`; a pose and a
     track are linked only if at least `min_kpts` (default max(1, (K + 2) // 3)) key points visible in both lie
     within the distance at which their OKS term is `match_thr`.  `sigmas`: K per-key-point OKS sigmas; built in
-    for K = 17 (COCO), 15 (PoseTrack) and 14 (CrowdPose)."""
+    for K = 17 (COCO), 15 (PoseTrack) and 14 (CrowdPose).
+
+    `motion`: None, or 'constant_velocity': a track keeps a velocity (one for the whole pose, 1/16 quarter pixel per
+    frame), the mean displacement of the co-visible key points per frame at every match, mixed into the old one with
+    weight `velocity_gain` / 16 (an integer 1 .. 16); a pose is compared with the track's points moved by velocity x
+    min(frames since its last match, `max_predict`) (an integer 0 .. 255; None: min(max_age, 255)); a track matched
+    only once has no velocity yet, and its agreement test is `new_gate` (an integer 1 .. 16) times wider in C[k],
+    sqrt(new_gate) times in distance.  The three are arguments of the motion model: given without it they raise."""
 
     def __init__(self, K, cameras=1, max_tracks=128, max_age=30, match_thr=0.5, min_kpts=None, score_thr=0.3,
-                 kpt_thr=0., sigmas=None):
+                 kpt_thr=0., sigmas=None, motion=None, velocity_gain=None, max_predict=None, new_gate=None):
         K = int(K)
         if not 1 <= K <= native.TRACK_MAX_K:
             raise ValueError(f'PoseTracker: K in 1 .. {native.TRACK_MAX_K}, got {K}')
@@ -75,6 +87,23 @@ class PoseTracker:
         self.K, self.cameras, self.max_tracks, self.max_age = K, int(cameras), int(max_tracks), int(max_age)
         self.min_kpts, self.score_thr, self.kpt_thr = int(min_kpts), float(score_thr), float(kpt_thr)
         self.match_thr = float(match_thr)
+        if motion not in (None, 'constant_velocity'):
+            raise ValueError(f"PoseTracker: motion is None or 'constant_velocity', got {motion!r}")
+        if motion is None:
+            given = [n for n, v in (('velocity_gain', velocity_gain), ('max_predict', max_predict),
+                                    ('new_gate', new_gate)) if v is not None]
+            if given:
+                raise ValueError(f'PoseTracker: {", ".join(given)} given with motion=None: they are arguments of '
+                                 "motion='constant_velocity'")
+        else:
+            velocity_gain = 8 if velocity_gain is None else velocity_gain
+            new_gate = 4 if new_gate is None else new_gate
+            max_predict = min(self.max_age, 255) if max_predict is None else max_predict
+            for name, v, lo, hi in (('velocity_gain', velocity_gain, 1, 16), ('max_predict', max_predict, 0, 255),
+                                    ('new_gate', new_gate, 1, 16)):
+                if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                    raise ValueError(f'PoseTracker: {name} is an integer in {lo} .. {hi}, got {v!r}')
+        self.motion, self.velocity_gain, self.max_predict, self.new_gate = motion, velocity_gain, max_predict, new_gate
         self._state = self._scratch = None
 
     def _allocate(self, dev):
@@ -84,6 +113,8 @@ class PoseTracker:
                            kpts=torch.zeros((C, M, K, 2), **z), vis=torch.zeros((C, M), **z),
                            area=torch.zeros((C, M), **z), frame=torch.zeros((C,), **z), next_id=torch.ones((C,), **z),
                            dropped=torch.zeros((C,), **z))
+        if self.motion is not None:
+            self._state.update(vel=torch.zeros((C, M, 2), **z), hits=torch.zeros((C, M), **z))
         self._scratch = ops.track_scratch(dev)
 
     def _camera(self, camera, who):
@@ -119,8 +150,10 @@ class PoseTracker:
         entries = [(kp, bb, keep, c, sc) for (kp, bb, keep), c, sc in zip(poses, cams, scales)]
         if self._state is None:
             self._allocate(dev)
+        motion = None if self.motion is None else (self._state['vel'], self._state['hits'], self.velocity_gain,
+                                                   self.max_predict, self.new_gate)
         return ops.track_poses(entries, self._state, self._scratch, self.C, min_kpts=self.min_kpts,
-                               max_age=self.max_age, score_thr=self.score_thr, kpt_thr=self.kpt_thr)
+                               max_age=self.max_age, score_thr=self.score_thr, kpt_thr=self.kpt_thr, motion=motion)
 
     def update(self, result, scale_factor=None, camera=0):
         """One frame of `camera` -> int32 [N] ids on the device, 0 = not tracked."""
@@ -128,7 +161,8 @@ class PoseTracker:
 
     def reset(self, camera=None):
         """Frees the slots of `camera` (None: of every camera); its ids restart at 1 and its frame count and drop
-        count at 0.  The state tensors stay where they are."""
+        count at 0.  The state tensors stay where they are (a birth writes a slot's velocity and hits, and a free
+        slot's are never read)."""
         if camera is not None:
             camera = self._camera(camera, 'PoseTracker.reset')
         if self._state is None:
@@ -140,7 +174,8 @@ class PoseTracker:
     def state(self, camera=0):
         """Views of one camera's state on the device: id, last, area [M] (id 0 = free slot; its other fields mean
         nothing), vis [M] (bit k = key point k visible; the uint32 mask as int32), kpts [M, K, 2] quarter pixels,
-        frame, next_id, dropped (0-d).  None before the first update."""
+        frame, next_id, dropped (0-d); with a motion model also vel [M, 2] (1/16 quarter pixel per frame) and hits
+        [M] (the matches of the track, its birth included).  None before the first update."""
         camera = self._camera(camera, 'PoseTracker.state')
         if self._state is None:
             return None
