@@ -608,6 +608,56 @@ typedef struct pave_track_motion_plan {
 int pave_track_poses_motion(const pave_track_motion_plan* plan, void* stream);
 
 /*
+ * Steady poses: a per-track adaptive exponential filter on the key points and box corners of tracked poses
+ * (pavenet_amd/csrc/pave_smooth.hip; the rule is DESIGN section 16, integer-exact), one launch for `entries` frames
+ * of any of `cameras` cameras.  The plan is copied into the kernel's arguments.  One block per camera of the launch
+ * takes that camera's entries in plan order: entries of one camera are in time order.
+ *   kpts[i], bboxes[i], keep[i], n[i], camera[i], scale[i]   as in pave_track_plan
+ *   ids[i]         DEVICE [n[i]] int32, in: the track id of every pose (what pave_track_poses wrote, or any ids);
+ *                  a pose is filtered iff it is valid, its id is >= 1, no valid pose before it in the frame has the
+ *                  same id, and a slot holds or can take the id
+ *   out_kpts[i]    DEVICE [n[i], K, 3] fp32, out;  out_bboxes[i] [n[i], 5] fp32, out: the poses in ORIGINAL-IMAGE
+ *                  pixels (scale (1, 1) downstream), coordinates multiples of 1/64: the filter's position of a
+ *                  filtered pose, the quarter-pixel quantisation of any other pose with finite coordinates, the quiet
+ *                  NaN 0x7fc00000 in a pose with a coordinate that is not finite; scores are copied bit for bit.
+ *                  Neither may overlap an input.  All six may be NULL where n[i] == 0 (the frame still counts)
+ *   the state, DEVICE, read and written: slot_id, slot_last [cameras, S] int32 (id 0: a free slot, its other fields
+ *                  are never read), slot_pos, slot_vel [cameras, S, K + 2, 2] int32 (1/64 pixel, 1/64 pixel per
+ *                  frame; the K key points, then the box corners; a point with pos x < 0 is uninitialised and its
+ *                  other three values are never read); frame, dropped [cameras] int32
+ *   alpha_min      1 .. 256: the filter's gain at rest, in 1/256
+ *   beta           0 .. 4096: how fast the gain rises with a point's speed (1/16 per 1/1024 of the pose's size per
+ *                  frame)
+ *   velocity_gain  1 .. 16, sixteenths: the weight of the newest measured velocity of a point
+ * Refused with PAVE_E_ARG before any device call: a null plan or state tensor, a null kpts, bboxes, ids, out_kpts or
+ * out_bboxes where n[i] > 0, entries outside 1 .. 32, n[i] outside 0 .. 128, K outside 1 .. 32, S outside 1 .. 128,
+ * cameras outside 1 .. 4096, a camera index outside [0, cameras), a scale that is not positive and finite, alpha_min,
+ * beta or velocity_gain outside its range, max_age < 0.  Slot indices come from the plan's counts and the arithmetic
+ * is 64-bit on whatever int32 the state holds: a plan that passes cannot address memory outside its tensors, whatever
+ * the poses, the ids and the stored state are.
+ */
+typedef struct pave_smooth_plan {
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  float*         out_kpts[PAVE_TRACK_MAX_FRAMES];
+  float*         out_bboxes[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int32_t* slot_id;
+  int32_t* slot_last;
+  int32_t* slot_pos;
+  int32_t* slot_vel;
+  int32_t* frame;
+  int32_t* dropped;
+  int entries, cameras, S, K, alpha_min, beta, velocity_gain, max_age;
+  float score_thr, kpt_thr;
+} pave_smooth_plan;
+int pave_smooth_poses(const pave_smooth_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

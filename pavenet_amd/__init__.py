@@ -41,4 +41,7 @@ def __getattr__(name):
     if name == 'PoseTracker':
         from . import tracking
         return tracking.PoseTracker
+    if name == 'PoseSmoother':
+        from . import smoothing
+        return smoothing.PoseSmoother
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

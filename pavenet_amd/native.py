@@ -181,6 +181,20 @@ class TrackMotionPlan(ctypes.Structure):
                 ('gain', ctypes.c_int), ('max_predict', ctypes.c_int), ('new_gate', ctypes.c_int)]
 
 
+class SmoothPlan(ctypes.Structure):
+    """`pave_smooth_plan` of include/pave_hip.h (the by-value argument of pave_smooth_poses)."""
+    _fields_ = [('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('n', ctypes.c_int * TRACK_MAX_FRAMES), ('camera', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES), ('slot_id', ctypes.c_void_p),
+                ('slot_last', ctypes.c_void_p), ('slot_pos', ctypes.c_void_p), ('slot_vel', ctypes.c_void_p),
+                ('frame', ctypes.c_void_p), ('dropped', ctypes.c_void_p), ('entries', ctypes.c_int),
+                ('cameras', ctypes.c_int), ('S', ctypes.c_int), ('K', ctypes.c_int), ('alpha_min', ctypes.c_int),
+                ('beta', ctypes.c_int), ('velocity_gain', ctypes.c_int), ('max_age', ctypes.c_int),
+                ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
+
+
 _lib = None
 
 

@@ -898,6 +898,98 @@ def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0
     return ids
 
 
+_SMOOTH_STATE = (('id', 1), ('last', 1), ('pos', 2), ('vel', 2), ('frame', 0), ('dropped', 0))
+# name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, K + 2, 2]
+
+
+def smooth_poses(entries, state, *, max_age=30, alpha_min=32, beta=128, velocity_gain=3, score_thr=0.3, kpt_thr=0.):
+    """Steady poses for frames of tracked poses, one launch per 32 frames (pave_smooth_poses; the rule is DESIGN
+    section 16).  entries: one (kpts [N, K, 3] fp32, bboxes [N, 5] fp32, keep [N] int32 or None, ids [N] int32,
+    camera, (sx, sy)) per frame, N <= 128, the frames of one camera in time order; state: int32 device tensors id,
+    last [cameras, S], pos, vel [cameras, S, K + 2, 2] (1/64 pixel, and per frame), frame, dropped [cameras], read
+    and written; alpha_min 1 .. 256, beta 0 .. 4096 and velocity_gain 1 .. 16 are integers.  Returns one (out_kpts
+    [N, K, 3], out_bboxes [N, 5]) pair of new fp32 tensors per entry, in original-image pixels.  Shapes, types and
+    ranges raise ValueError before anything is asked of a device."""
+    who = 'smooth_poses'
+    entries = list(entries)
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name, _ in _SMOOTH_STATE):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(n for n, _ in _SMOOTH_STATE)}')
+    if state['pos'].dim() != 4 or state['pos'].shape[3] != 2 or state['pos'].shape[2] < 3:
+        raise ValueError(f'{who}: state pos must be [cameras, S, K + 2, 2], got {tuple(state["pos"].shape)}')
+    cameras, S, J = state['pos'].shape[:3]
+    K = J - 2
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS
+            and 1 <= K <= native.TRACK_MAX_K):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS}, S in 1 .. {native.TRACK_MAX_TRACKS} and K '
+                         f'in 1 .. {native.TRACK_MAX_K}, got {cameras}, {S} and {K}')
+    dev = state['pos'].device
+    for name, kind in _SMOOTH_STATE:
+        t = state[name]
+        want = ((cameras,), (cameras, S), (cameras, S, J, 2))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    for name, v, lo, hi in (('alpha_min', alpha_min, 1, 256), ('beta', beta, 0, 4096),
+                            ('velocity_gain', velocity_gain, 1, 16)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    checked = []
+    for i, entry in enumerate(entries):
+        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
+            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
+        kpts, bboxes, keep, ids, camera, scale = entry
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
+            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
+        if N > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+        try:
+            sx, sy = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
+        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
+        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    # the shapes are right: now where the tensors live
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n, _ in _SMOOTH_STATE):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if any(t is not None and t.device != dev for t in c[:4]):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    outs = [(torch.empty((c[7], K, 3), dtype=torch.float32, device=dev),
+             torch.empty((c[7], 5), dtype=torch.float32, device=dev)) for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.SmoothPlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
+            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+                _ptr(keep) or None, _ptr(ids) or None
+            plan.out_kpts[i], plan.out_bboxes[i] = (t.data_ptr() or None for t in outs[at + i])
+            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+        plan.slot_id, plan.slot_last, plan.slot_pos, plan.slot_vel, plan.frame, plan.dropped = (
+            state[n].data_ptr() for n, _ in _SMOOTH_STATE)
+        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
+        plan.alpha_min, plan.beta, plan.velocity_gain, plan.max_age = alpha_min, beta, velocity_gain, int(max_age)
+        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        _launch('pave_smooth_poses', who, dev, ctypes.byref(plan))
+    return outs
+
+
 def fuse_sum_nhwc(terms, relu=True):
     """HRNet fuse layer in one pass (pave_fuse_sum_nhwc_f32): terms = [(map, shift), ...] (1..4), map
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones

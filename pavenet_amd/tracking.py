@@ -8,8 +8,8 @@ With ``motion='constant_velocity'`` (section 14, "Motion") a track also keeps a 
 and smoothed, and a pose is compared with where the track is predicted to be, so links survive fast walks, gaps
 and crossings.  The default, ``motion=None``, is the plain rule.
 
-Not built: Kalman filtering, per-key-point velocities, appearance re-identification, cross-camera identities,
-optimal assignment.
+Not built: Kalman filtering, per-key-point velocities (``smoothing.PoseSmoother`` keeps them, for the picture only),
+appearance re-identification, cross-camera identities, optimal assignment.
 """
 import math
 
