@@ -658,6 +658,97 @@ typedef struct pave_smooth_plan {
 int pave_smooth_poses(const pave_smooth_plan* plan, void* stream);
 
 /*
+ * Zones and counting lines: which tracks are inside which polygon, for how long, and which directed line a track
+ * crossed (pavenet_amd/csrc/pave_zones.hip; the rule is DESIGN section 17, integer-exact), one launch for `entries`
+ * frames of any of `cameras` cameras.  The plan is copied into the kernel's arguments.  One block per camera of the
+ * launch takes that camera's entries in plan order: entries of one camera are in time order.
+ *   kpts[i], bboxes[i], keep[i], n[i], camera[i], scale[i]   as in pave_track_plan;  ids[i] as in pave_smooth_plan
+ *   out_zones[i]     DEVICE [n[i]] int32, out: bit z set iff the pose's track is inside zone z (0: takes no part)
+ *   out_dwell[i]     DEVICE [n[i], 8] int32, out: frames the track has been inside zone z, 0 where it is not
+ *   out_events[i]    DEVICE [max_events, 5] int32, out: the frame's events (kind, index, id, pose, frame) in the
+ *                    rule's fixed order, the first max_events of them; rows past the count are zero
+ *   out_n_events[i]  DEVICE [1] int32, out: ALL events of the frame (it may exceed max_events)
+ *                    out_zones and out_dwell may be NULL where n[i] == 0 (the frame still counts)
+ *   the state, DEVICE int32, read and written: slot_id, slot_last, slot_inside, slot_alerted [cameras, S] (id 0: a
+ *                    free slot, its other fields are never read), slot_pos [cameras, S, 2] (1/8 pixel), slot_streak,
+ *                    slot_since [cameras, S, 8]; frame, dropped [cameras];
+ *                    counters [cameras, PAVE_ZONE_COUNTER_WORDS]: occupancy, entered, exited, appeared, vanished
+ *                    [8] at PAVE_ZONE_CNT_*, crossed [8, 2] (forward, backward) at PAVE_ZONE_CNT_CROSSED
+ *   geometry         DEVICE [cameras, PAVE_ZONE_GEOM_WORDS] int32, read only: the number of zones and of lines, the
+ *                    vertex count and dwell_frames of every zone, the zones' vertices [8, 16, 2] and the lines' ends
+ *                    [8, 2, 2] (A, B), in 1/8 pixel, at PAVE_ZONE_GEOM_*.  Counts are clamped to 0 .. 8 and 0 .. 16
+ *                    as they are read
+ *   anchor           PAVE_ZONE_ANCHOR_FEET | _BOX | _CENTRE;  anchor_kpt[0 .. n_anchor): the key points of 'feet'
+ *   min_frames       1 .. 255: the frames a raw inside test must disagree before the bit flips
+ * Refused with PAVE_E_ARG before any device call: whatever pave_smooth_poses refuses in the fields of the same name
+ * (a null plan or state tensor, a null kpts, bboxes or ids where n[i] > 0, entries outside 1 .. 32, n[i] outside
+ * 0 .. 128, K outside 1 .. 32, S outside 1 .. 128, cameras outside 1 .. 4096, a camera index outside [0, cameras), a
+ * scale that is not positive and finite, max_age < 0), a null counters or geometry tensor, a null out_zones or
+ * out_dwell where n[i] > 0, a null out_events or out_n_events, min_frames outside 1 .. 255, max_events outside
+ * 1 .. 4096, an anchor outside 0 .. 2, n_anchor outside 0 .. 4, an anchor_kpt outside [0, K).  Every loop bound is
+ * from the plan or the maxima below: a plan that passes cannot address memory outside its tensors, whatever the
+ * poses, the ids, the stored state and the geometry hold.
+ */
+#define PAVE_ZONE_MAX_ZONES 8
+#define PAVE_ZONE_MAX_LINES 8
+#define PAVE_ZONE_MAX_VERTICES 16
+#define PAVE_ZONE_MAX_ANCHOR_KPTS 4
+#define PAVE_ZONE_MAX_EVENTS 4096
+#define PAVE_ZONE_EVENT_WORDS 5
+#define PAVE_ZONE_ENTER 1
+#define PAVE_ZONE_EXIT 2
+#define PAVE_ZONE_DWELL 3
+#define PAVE_ZONE_APPEAR 4
+#define PAVE_ZONE_VANISH 5
+#define PAVE_ZONE_CROSS_FWD 6
+#define PAVE_ZONE_CROSS_BACK 7
+#define PAVE_ZONE_ANCHOR_FEET 0
+#define PAVE_ZONE_ANCHOR_BOX 1
+#define PAVE_ZONE_ANCHOR_CENTRE 2
+#define PAVE_ZONE_CNT_OCCUPANCY 0
+#define PAVE_ZONE_CNT_ENTERED 8
+#define PAVE_ZONE_CNT_EXITED 16
+#define PAVE_ZONE_CNT_APPEARED 24
+#define PAVE_ZONE_CNT_VANISHED 32
+#define PAVE_ZONE_CNT_CROSSED 40
+#define PAVE_ZONE_COUNTER_WORDS 56
+#define PAVE_ZONE_GEOM_NZONES 0
+#define PAVE_ZONE_GEOM_NLINES 1
+#define PAVE_ZONE_GEOM_NVERT 2
+#define PAVE_ZONE_GEOM_DWELL 10
+#define PAVE_ZONE_GEOM_ZONES 18
+#define PAVE_ZONE_GEOM_LINES 274
+#define PAVE_ZONE_GEOM_WORDS 306
+typedef struct pave_zone_plan {
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_zones[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_dwell[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_events[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_n_events[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int32_t* slot_id;
+  int32_t* slot_last;
+  int32_t* slot_pos;
+  int32_t* slot_inside;
+  int32_t* slot_alerted;
+  int32_t* slot_streak;
+  int32_t* slot_since;
+  int32_t* frame;
+  int32_t* dropped;
+  int32_t* counters;
+  const int32_t* geometry;
+  int anchor_kpt[PAVE_ZONE_MAX_ANCHOR_KPTS];
+  int entries, cameras, S, K, anchor, n_anchor, min_frames, max_events, max_age;
+  float score_thr, kpt_thr;
+} pave_zone_plan;
+int pave_zone_events(const pave_zone_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

@@ -44,4 +44,7 @@ def __getattr__(name):
     if name == 'PoseSmoother':
         from . import smoothing
         return smoothing.PoseSmoother
+    if name == 'ZoneMonitor':
+        from . import zones
+        return zones.ZoneMonitor
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

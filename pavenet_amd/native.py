@@ -195,6 +195,30 @@ class SmoothPlan(ctypes.Structure):
                 ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
 
 
+ZONE_MAX_ZONES, ZONE_MAX_LINES, ZONE_MAX_VERTICES, ZONE_MAX_ANCHOR_KPTS, ZONE_MAX_EVENTS = (
+    DEFINES['PAVE_ZONE_MAX_' + n] for n in ('ZONES', 'LINES', 'VERTICES', 'ANCHOR_KPTS', 'EVENTS'))
+ZONE_EVENT_WORDS, ZONE_COUNTER_WORDS, ZONE_GEOM_WORDS = (
+    DEFINES['PAVE_ZONE_' + n] for n in ('EVENT_WORDS', 'COUNTER_WORDS', 'GEOM_WORDS'))
+
+
+class ZonePlan(ctypes.Structure):
+    """`pave_zone_plan` of include/pave_hip.h (the by-value argument of pave_zone_events)."""
+    _fields_ = [('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_zones', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_dwell', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_events', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_n_events', ctypes.c_void_p * TRACK_MAX_FRAMES), ('n', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('camera', ctypes.c_int * TRACK_MAX_FRAMES), ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES),
+                ('slot_id', ctypes.c_void_p), ('slot_last', ctypes.c_void_p), ('slot_pos', ctypes.c_void_p),
+                ('slot_inside', ctypes.c_void_p), ('slot_alerted', ctypes.c_void_p), ('slot_streak', ctypes.c_void_p),
+                ('slot_since', ctypes.c_void_p), ('frame', ctypes.c_void_p), ('dropped', ctypes.c_void_p),
+                ('counters', ctypes.c_void_p), ('geometry', ctypes.c_void_p),
+                ('anchor_kpt', ctypes.c_int * ZONE_MAX_ANCHOR_KPTS), ('entries', ctypes.c_int),
+                ('cameras', ctypes.c_int), ('S', ctypes.c_int), ('K', ctypes.c_int), ('anchor', ctypes.c_int),
+                ('n_anchor', ctypes.c_int), ('min_frames', ctypes.c_int), ('max_events', ctypes.c_int),
+                ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
+
+
 _lib = None
 
 

@@ -990,6 +990,119 @@ def smooth_poses(entries, state, *, max_age=30, alpha_min=32, beta=128, velocity
     return outs
 
 
+_ZONE_STATE = (('id', 1), ('last', 1), ('pos', 2), ('inside', 1), ('alerted', 1), ('streak', 3), ('since', 3),
+               ('frame', 0), ('dropped', 0), ('counters', 4), ('geometry', 5))
+# name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 8], 4 [cameras, 56], 5 [cameras, 306]
+ZONE_ANCHORS = ('feet', 'box', 'centre')       # PAVE_ZONE_ANCHOR_*
+
+
+def zone_events(entries, state, *, K, max_age=30, anchor='feet', anchor_kpts=(), min_frames=2, max_events=256,
+                score_thr=0.3, kpt_thr=0.):
+    """Zone and line events for frames of tracked poses, one launch per 32 frames (pave_zone_events; the rule is
+    DESIGN section 17).  entries: one (kpts [N, K, 3] fp32, bboxes [N, 5] fp32, keep [N] int32 or None, ids [N] int32,
+    camera, (sx, sy)) per frame, N <= 128, the frames of one camera in time order; state: int32 device tensors id,
+    last, inside, alerted [cameras, S], pos [cameras, S, 2] (1/8 pixel), streak, since [cameras, S, 8], frame, dropped
+    [cameras], counters [cameras, 56], read and written, and geometry [cameras, 306], read (the layouts are
+    PAVE_ZONE_CNT_* and PAVE_ZONE_GEOM_* of include/pave_hip.h); anchor 'feet' | 'box' | 'centre', anchor_kpts at
+    most 4 key points in [0, K), min_frames 1 .. 255, max_events 1 .. 4096.  Returns one dict(zones [N], dwell [N, 8],
+    events [max_events, 5], n_events 0-d) of new int32 tensors per entry.  Shapes, types and ranges raise ValueError
+    before anything is asked of a device."""
+    who = 'zone_events'
+    entries = list(entries)
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name, _ in _ZONE_STATE):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(n for n, _ in _ZONE_STATE)}')
+    if state['pos'].dim() != 3 or state['pos'].shape[2] != 2:
+        raise ValueError(f'{who}: state pos must be [cameras, S, 2], got {tuple(state["pos"].shape)}')
+    cameras, S = state['pos'].shape[:2]
+    if isinstance(K, bool) or not isinstance(K, int):
+        raise ValueError(f'{who}: K must be an integer, got {K!r}')
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS
+            and 1 <= K <= native.TRACK_MAX_K):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS}, S in 1 .. {native.TRACK_MAX_TRACKS} and K '
+                         f'in 1 .. {native.TRACK_MAX_K}, got {cameras}, {S} and {K}')
+    dev = state['pos'].device
+    for name, kind in _ZONE_STATE:
+        t = state[name]
+        want = ((cameras,), (cameras, S), (cameras, S, 2), (cameras, S, native.ZONE_MAX_ZONES),
+                (cameras, native.ZONE_COUNTER_WORDS), (cameras, native.ZONE_GEOM_WORDS))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    for name, v, lo, hi in (('min_frames', min_frames, 1, 255), ('max_events', max_events, 1, native.ZONE_MAX_EVENTS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    if anchor not in ZONE_ANCHORS:
+        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
+    anchor_kpts = list(anchor_kpts)
+    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
+            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
+        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
+                         f'{anchor_kpts!r}')
+    checked = []
+    for i, entry in enumerate(entries):
+        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
+            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
+        kpts, bboxes, keep, ids, camera, scale = entry
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
+            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
+        if N > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+        try:
+            sx, sy = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
+        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
+        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    # the shapes are right: now where the tensors live
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n, _ in _ZONE_STATE):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if any(t is not None and t.device != dev for t in c[:4]):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    z = dict(dtype=torch.int32, device=dev)
+    outs = [dict(zones=torch.empty((c[7],), **z), dwell=torch.empty((c[7], native.ZONE_MAX_ZONES), **z),
+                 events=torch.empty((max_events, native.ZONE_EVENT_WORDS), **z), n_events=torch.empty((), **z))
+            for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.ZonePlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
+            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+                _ptr(keep) or None, _ptr(ids) or None
+            out = outs[at + i]
+            plan.out_zones[i], plan.out_dwell[i] = out['zones'].data_ptr() or None, out['dwell'].data_ptr() or None
+            plan.out_events[i], plan.out_n_events[i] = out['events'].data_ptr(), out['n_events'].data_ptr()
+            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+        (plan.slot_id, plan.slot_last, plan.slot_pos, plan.slot_inside, plan.slot_alerted, plan.slot_streak,
+         plan.slot_since, plan.frame, plan.dropped, plan.counters, plan.geometry) = (
+            state[n].data_ptr() for n, _ in _ZONE_STATE)
+        for i, k in enumerate(anchor_kpts):
+            plan.anchor_kpt[i] = k
+        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
+        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
+        plan.min_frames, plan.max_events, plan.max_age = min_frames, max_events, int(max_age)
+        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        _launch('pave_zone_events', who, dev, ctypes.byref(plan))
+    return outs
+
+
 def fuse_sum_nhwc(terms, relu=True):
     """HRNet fuse layer in one pass (pave_fuse_sum_nhwc_f32): terms = [(map, shift), ...] (1..4), map
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones
