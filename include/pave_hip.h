@@ -749,6 +749,86 @@ typedef struct pave_zone_plan {
 int pave_zone_events(const pave_zone_plan* plan, void* stream);
 
 /*
+ * The same person again: a colour descriptor per pose read from the pixels under it, and a gallery per camera that
+ * maps track ids to person ids which survive a gap (pavenet_amd/csrc/pave_reid.hip; the rule is DESIGN section 18,
+ * integer-exact).  The plans are copied into the kernels' arguments; the surfaces are read only.
+ *
+ * pave_reid_describe_nv12 / _bgr: one launch, one workgroup per (entry, pose, region); region 0 the torso, 1 the legs.
+ *   src[i]     DEVICE uint8, read only: an NV12 surface [height * 3 / 2, pitch] whose first `width` columns are the
+ *              picture, or a BGR picture [height, width, 3] with pitch = 3 width
+ *   kpts[i], bboxes[i], keep[i], n[i], scale[i]   as in pave_track_plan
+ *   hist[i]    DEVICE [n[i], 2, 256] int32, out: the normalised descriptor (h[b] * 128) / count of every region, bin
+ *              (y * 8 + u) * 8 + v; zero where the region is invalid
+ *   count[i]   DEVICE [n[i], 2] int32, out: the samples of the region, 0 where it is invalid (a pose without keep,
+ *              with a box score <= score_thr or a coordinate that is not finite; no visible key point of one of its
+ *              two parts and no fallback; wholly off the picture; fewer than PAVE_REID_MIN_SAMPLES samples)
+ *   part[r][h][0 .. n_part[r][h])   the key points of region r: h = 0 its upper part (torso: shoulders, legs: hips),
+ *              h = 1 its lower part (hips, knees)
+ * pave_reid_update_nv12 / _bgr: two launches, that one into hist and count (here scratch areas of the caller), then
+ * one workgroup per camera of the launch, which takes that camera's entries in plan order: entries of one camera are
+ * in time order.
+ *   ids[i]     DEVICE [n[i]] int32, in: the track id of every pose;  camera[i] whose gallery entry i reads and writes
+ *   out_ids[i] DEVICE [n[i]] int32, out: the person id of every pose, 0 where it takes no part or was dropped
+ *   out_sim[i] DEVICE [n[i]] int32, out: the score at which the pose was re-identified in this frame, else 0
+ *   the gallery, DEVICE int32, read and written: person, track, last [cameras, S] (person 0: a free slot, its other
+ *              fields are never read), hits [cameras, S, 2], hist [cameras, S, 2, 256]; frame, next, dropped [cameras]
+ *   pairs      DEVICE, PAVE_TRACK_MAX_FRAMES x 128 x 128 int32 (2 MiB): the pair scores of every block
+ *   match_thr  0 .. PAVE_REID_NEVER (which no score reaches);  min_hits 1 .. PAVE_REID_MAX_HITS;  gain 1 .. 16
+ * Refused with PAVE_E_ARG before any device call: a null plan, a null surface, hist or count, a null kpts or bboxes
+ * where n[i] > 0, entries outside 1 .. 32, n[i] outside 0 .. 128, K outside 1 .. 32, width or height outside
+ * 1 .. 8192, odd NV12 sizes, a pitch below a row's bytes (BGR: other than 3 width), a scale that is not positive and
+ * finite, an n_part outside 0 .. 4, a part index outside [0, K); by the update entries also a null ids, out_ids or
+ * out_sim where n[i] > 0, a null gallery tensor or pairs area, S outside 1 .. 128, cameras outside 1 .. 4096, a
+ * camera index outside [0, cameras), max_lost < 0, match_thr, min_hits or gain outside its range.  Sample addresses
+ * are clipped to the picture and slot indices are loop counters of the plan's counts: a plan that passes cannot
+ * address memory outside its tensors, whatever the poses, ids, state and pixels hold.
+ */
+#define PAVE_REID_BINS 256
+#define PAVE_REID_CAP 1024
+#define PAVE_REID_MIN_SAMPLES 16
+#define PAVE_REID_MAX_PART 4
+#define PAVE_REID_MAX_HITS 32767
+#define PAVE_REID_NEVER 65537
+typedef struct pave_reid_describe_plan {
+  const uint8_t* src[PAVE_TRACK_MAX_FRAMES];
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       hist[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       count[PAVE_TRACK_MAX_FRAMES];
+  int            pitch[PAVE_TRACK_MAX_FRAMES];
+  int            width[PAVE_TRACK_MAX_FRAMES];
+  int            height[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int part[2][2][PAVE_REID_MAX_PART];
+  int n_part[2][2];
+  int entries, K;
+  float score_thr, kpt_thr;
+} pave_reid_describe_plan;
+typedef struct pave_reid_plan {
+  pave_reid_describe_plan d;
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_sim[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  int32_t* person;
+  int32_t* track;
+  int32_t* last;
+  int32_t* hits;
+  int32_t* hist;
+  int32_t* frame;
+  int32_t* next;
+  int32_t* dropped;
+  int32_t* pairs;
+  int cameras, S, max_lost, match_thr, min_hits, gain;
+} pave_reid_plan;
+int pave_reid_describe_nv12(const pave_reid_describe_plan* plan, void* stream);
+int pave_reid_describe_bgr(const pave_reid_describe_plan* plan, void* stream);
+int pave_reid_update_nv12(const pave_reid_plan* plan, void* stream);
+int pave_reid_update_bgr(const pave_reid_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

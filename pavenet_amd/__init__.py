@@ -47,4 +47,7 @@ def __getattr__(name):
     if name == 'ZoneMonitor':
         from . import zones
         return zones.ZoneMonitor
+    if name == 'PersonReID':
+        from . import reid
+        return reid.PersonReID
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -219,6 +219,34 @@ class ZonePlan(ctypes.Structure):
                 ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
 
 
+REID_BINS, REID_CAP, REID_MIN_SAMPLES, REID_MAX_PART, REID_MAX_HITS, REID_NEVER = (
+    DEFINES['PAVE_REID_' + n] for n in ('BINS', 'CAP', 'MIN_SAMPLES', 'MAX_PART', 'MAX_HITS', 'NEVER'))
+
+
+class ReidDescribePlan(ctypes.Structure):
+    """`pave_reid_describe_plan` of include/pave_hip.h (the by-value argument of pave_reid_describe_nv12 / _bgr)."""
+    _fields_ = [('src', ctypes.c_void_p * TRACK_MAX_FRAMES), ('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES), ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('hist', ctypes.c_void_p * TRACK_MAX_FRAMES), ('count', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('pitch', ctypes.c_int * TRACK_MAX_FRAMES), ('width', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('height', ctypes.c_int * TRACK_MAX_FRAMES), ('n', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES),
+                ('part', ((ctypes.c_int * REID_MAX_PART) * 2) * 2), ('n_part', (ctypes.c_int * 2) * 2),
+                ('entries', ctypes.c_int), ('K', ctypes.c_int), ('score_thr', ctypes.c_float),
+                ('kpt_thr', ctypes.c_float)]
+
+
+class ReidPlan(ctypes.Structure):
+    """`pave_reid_plan` of include/pave_hip.h (the by-value argument of pave_reid_update_nv12 / _bgr)."""
+    _fields_ = [('d', ReidDescribePlan), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_ids', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_sim', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('camera', ctypes.c_int * TRACK_MAX_FRAMES), ('person', ctypes.c_void_p), ('track', ctypes.c_void_p),
+                ('last', ctypes.c_void_p), ('hits', ctypes.c_void_p), ('hist', ctypes.c_void_p),
+                ('frame', ctypes.c_void_p), ('next', ctypes.c_void_p), ('dropped', ctypes.c_void_p),
+                ('pairs', ctypes.c_void_p), ('cameras', ctypes.c_int), ('S', ctypes.c_int), ('max_lost', ctypes.c_int),
+                ('match_thr', ctypes.c_int), ('min_hits', ctypes.c_int), ('gain', ctypes.c_int)]
+
+
 _lib = None
 
 

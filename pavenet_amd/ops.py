@@ -1103,6 +1103,163 @@ def zone_events(entries, state, *, K, max_age=30, anchor='feet', anchor_kpts=(),
     return outs
 
 
+_REID_STATE = (('person', 1), ('track', 1), ('last', 1), ('hits', 2), ('hist', 3), ('frame', 0), ('next', 0),
+               ('dropped', 0))   # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 2, 256]
+
+
+def reid_scratch(device):
+    """The areas pave_reid_update_* works in, allocated once per gallery: the descriptors (8 MiB), the sample counts
+    and the pair scores (2 MiB) of the 32 entries of a launch."""
+    F, P, S = native.TRACK_MAX_FRAMES, native.TRACK_MAX_POSES, native.TRACK_MAX_TRACKS
+    z = dict(dtype=torch.int32, device=device)
+    return dict(hist=torch.empty((F, P, 2, native.REID_BINS), **z), count=torch.empty((F, P, 2), **z),
+                pairs=torch.empty((F, P, S), **z))
+
+
+def _reid_items(who, kind, items, K, parts):
+    """The checks reid_describe and reid_update share, all ValueError -> (geometry, parts)."""
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= native.TRACK_MAX_K:
+        raise ValueError(f'{who}: K must be an integer in 1 .. {native.TRACK_MAX_K}, got {K!r}')
+    try:
+        parts = [[[k for k in half] for half in region] for region in parts]
+    except TypeError:
+        parts = []
+    if len(parts) != 2 or any(len(region) != 2 for region in parts):
+        raise ValueError(f'{who}: parts is ((torso upper, torso lower), (legs upper, legs lower)) index lists')
+    for region in parts:
+        for half in region:
+            if len(half) > native.REID_MAX_PART or any(isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K
+                                                       for k in half):
+                raise ValueError(f'{who}: a part holds at most {native.REID_MAX_PART} integers in [0, {K}), got {half!r}')
+    geometry = _surface_geometry(who, kind, [tuple(it[:6]) + (0,) for it in items], K, 1)
+    for i, g in enumerate(geometry):
+        if g[3] > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {g[3]} poses, at most {native.TRACK_MAX_POSES}')
+    return geometry, parts
+
+
+def _reid_fill(d, part, geometry, hists, counts, K, parts, score_thr, kpt_thr):
+    """A pave_reid_describe_plan for the entries `part`."""
+    for i, it in enumerate(part):
+        pitch, W, H, N, sx, sy, _ = geometry[i]
+        d.src[i], d.kpts[i], d.bboxes[i], d.keep[i] = it[0].data_ptr(), _ptr(it[2]) or None, _ptr(it[3]) or None, \
+            _ptr(it[4]) or None
+        d.hist[i], d.count[i] = hists[i], counts[i]
+        d.pitch[i], d.width[i], d.height[i], d.n[i], d.scale[i][0], d.scale[i][1] = pitch, W, H, N, sx, sy
+    for r, region in enumerate(parts):
+        for h, half in enumerate(region):
+            d.n_part[r][h] = len(half)
+            for i, k in enumerate(half):
+                d.part[r][h][i] = k
+    d.entries, d.K, d.score_thr, d.kpt_thr = len(part), K, float(score_thr), float(kpt_thr)
+
+
+def reid_describe(kind, items, K, parts, *, score_thr=0.3, kpt_thr=0.):
+    """The colour descriptors of the poses on surfaces, one launch per 32 surfaces (pave_reid_describe_nv12 / _bgr; the
+    rule is DESIGN section 18).  kind and items: (surface, width, kpts, bboxes, keep, (sx, sy)) as in draw_poses, at
+    most 128 poses each; parts ((torso upper, torso lower), (legs upper, legs lower)): at most 4 key points each.
+    Returns one dict(hist [N, 2, 256], count [N, 2]) of new int32 tensors per item; the surfaces are only read.
+    Shapes, types and ranges raise ValueError before anything is asked of a device."""
+    who = 'reid_describe'
+    items = list(items)
+    geometry, parts = _reid_items(who, kind, items, K, parts)
+    dev = items[0][0].device
+    if dev.type != 'cuda':
+        raise ValueError(f'{who}: surface 0 must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    for i, it in enumerate(items):
+        if any(t is not None and (t.device != dev or not t.is_contiguous()) for t in (it[0], it[2], it[3], it[4])):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous and on one HIP device ({dev})')
+    z = dict(dtype=torch.int32, device=dev)
+    outs = [dict(hist=torch.empty((g[3], 2, native.REID_BINS), **z), count=torch.empty((g[3], 2), **z)) for g in geometry]
+    pad = torch.empty((1,), **z)    # (an empty tensor has no address; the entry asks for one)
+    for at in range(0, len(items), native.TRACK_MAX_FRAMES):
+        plan = native.ReidDescribePlan()
+        part = items[at:at + native.TRACK_MAX_FRAMES]
+        o = outs[at:at + native.TRACK_MAX_FRAMES]
+        _reid_fill(plan, part, geometry[at:], [v['hist'].data_ptr() or pad.data_ptr() for v in o],
+                   [v['count'].data_ptr() or pad.data_ptr() for v in o], K, parts, score_thr, kpt_thr)
+        _launch('pave_reid_describe_' + kind, who, dev, ctypes.byref(plan))
+    return outs
+
+
+def reid_update(kind, entries, state, scratch, K, parts, *, max_lost=900, match_thr, min_hits=3, gain=2, score_thr=0.3,
+                kpt_thr=0.):
+    """Person ids for frames of tracked poses, two launches per 32 frames (pave_reid_update_nv12 / _bgr; the rule is
+    DESIGN section 18).  entries: one (surface, width, kpts, bboxes, keep, (sx, sy), ids [N] int32, camera) per frame,
+    N <= 128, the frames of one camera in time order; state: int32 device tensors person, track, last [cameras, S],
+    hits [cameras, S, 2], hist [cameras, S, 2, 256], frame, next, dropped [cameras], read and written; scratch:
+    reid_scratch().  Returns one dict(ids [N], sim [N]) of new int32 tensors per entry.  Shapes, types and ranges
+    raise ValueError before anything is asked of a device."""
+    who = 'reid_update'
+    entries = list(entries)
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name, _ in _REID_STATE):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(n for n, _ in _REID_STATE)}')
+    if state['person'].dim() != 2:
+        raise ValueError(f'{who}: state person must be [cameras, S], got {tuple(state["person"].shape)}')
+    cameras, S = state['person'].shape
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS} and S in 1 .. {native.TRACK_MAX_TRACKS}, got '
+                         f'{cameras} and {S}')
+    dev = state['person'].device
+    for name, kind_ in _REID_STATE:
+        t = state[name]
+        want = ((cameras,), (cameras, S), (cameras, S, 2), (cameras, S, 2, native.REID_BINS))[kind_]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    for name, v, lo, hi in (('match_thr', match_thr, 0, native.REID_NEVER), ('min_hits', min_hits, 1, native.REID_MAX_HITS),
+                            ('gain', gain, 1, 16)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
+    if isinstance(max_lost, bool) or int(max_lost) != max_lost or max_lost < 0:
+        raise ValueError(f'{who}: max_lost must be an integer >= 0, got {max_lost!r}')
+    if any(not (isinstance(it, (tuple, list)) and len(it) == 8) for it in entries):
+        raise ValueError(f'{who}: an entry is (surface, width, kpts, bboxes, keep, (sx, sy), ids, camera)')
+    geometry, parts = _reid_items(who, kind, entries, K, parts)
+    for i, (it, g) in enumerate(zip(entries, geometry)):
+        ids, camera = it[6], it[7]
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (g[3],)
+                and ids.is_contiguous()):
+            raise ValueError(f'{who}: ids of entry {i} must be a contiguous [{g[3]}] int32 tensor')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+    want = reid_scratch('meta')
+    if not isinstance(scratch, dict) or any(
+            not isinstance(scratch.get(n), torch.Tensor) or scratch[n].shape != want[n].shape
+            or scratch[n].dtype != torch.int32 or not scratch[n].is_contiguous() for n in want):
+        raise ValueError(f'{who}: scratch is what reid_scratch() returns')
+    # the shapes are right: now where the tensors live
+    if dev.type != 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n, _ in _REID_STATE) or any(scratch[n].device != dev for n in want):
+        raise ValueError(f'{who}: the state and scratch tensors must be on one device ({dev})')
+    for i, it in enumerate(entries):
+        if any(t is not None and (t.device != dev or not t.is_contiguous()) for t in (it[0], it[2], it[3], it[4], it[6])):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous and on the HIP device of the state ({dev})')
+    z = dict(dtype=torch.int32, device=dev)
+    outs = [dict(ids=torch.empty((g[3],), **z), sim=torch.empty((g[3],), **z)) for g in geometry]
+    hist_at, count_at = scratch['hist'].data_ptr(), scratch['count'].data_ptr()
+    hist_step, count_step = scratch['hist'][0].numel() * 4, scratch['count'][0].numel() * 4
+    for at in range(0, len(entries), native.TRACK_MAX_FRAMES):
+        plan = native.ReidPlan()
+        part = entries[at:at + native.TRACK_MAX_FRAMES]
+        _reid_fill(plan.d, part, geometry[at:], [hist_at + i * hist_step for i in range(len(part))],
+                   [count_at + i * count_step for i in range(len(part))], K, parts, score_thr, kpt_thr)
+        for i, it in enumerate(part):
+            out = outs[at + i]
+            plan.ids[i], plan.out_ids[i], plan.out_sim[i] = it[6].data_ptr() or None, out['ids'].data_ptr() or None, \
+                out['sim'].data_ptr() or None
+            plan.camera[i] = int(it[7])
+        (plan.person, plan.track, plan.last, plan.hits, plan.hist, plan.frame, plan.next, plan.dropped) = (
+            state[n].data_ptr() for n, _ in _REID_STATE)
+        plan.pairs = scratch['pairs'].data_ptr()
+        plan.cameras, plan.S, plan.max_lost, plan.match_thr = cameras, S, int(max_lost), match_thr
+        plan.min_hits, plan.gain = min_hits, gain
+        _launch('pave_reid_update_' + kind, who, dev, ctypes.byref(plan))
+    return outs
+
+
 def fuse_sum_nhwc(terms, relu=True):
     """HRNet fuse layer in one pass (pave_fuse_sum_nhwc_f32): terms = [(map, shift), ...] (1..4), map
     [N, C, H >> shift, W >> shift] fp32 channels_last; returns relu(sum of the maps, the coarser ones

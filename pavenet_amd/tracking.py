@@ -9,7 +9,8 @@ and smoothed, and a pose is compared with where the track is predicted to be, so
 and crossings.  The default, ``motion=None``, is the plain rule.
 
 Not built: Kalman filtering, per-key-point velocities (``smoothing.PoseSmoother`` keeps them, for the picture only),
-appearance re-identification, cross-camera identities, optimal assignment.
+cross-camera identities, optimal assignment.  (Appearance re-identification is ``reid.PersonReID``, a stage after
+this one: DESIGN section 18.)
 """
 import math
 
