@@ -749,6 +749,66 @@ typedef struct pave_zone_plan {
 int pave_zone_events(const pave_zone_plan* plan, void* stream);
 
 /*
+ * Zones, counting lines and their live counts drawn into surfaces on the device (pavenet_amd/csrc/pave_overlay.hip;
+ * the rule is DESIGN section 19, integer-exact), one launch for n separately allocated surfaces of any sizes, in
+ * place.  The plan is copied into the kernel's arguments.  The monitor's tensors are only read.
+ *   dst, pitch, width, height, table: as in pave_draw_plan;  camera[i]: the camera whose geometry surface i shows
+ *   geometry, counters, slot_id, slot_alerted, slot_inside: DEVICE, the tensors of the same names of pave_zone_plan
+ *              ([cameras, PAVE_ZONE_GEOM_WORDS], [cameras, PAVE_ZONE_COUNTER_WORDS] and three [cameras, S]).  Counts
+ *              are clamped to 0 .. 8 and 0 .. 16 and vertex words to 0 .. 65535 as they are read; a zone without
+ *              vertices is not drawn
+ *   color[t]   rows 0 .. 7: the zones; 8 .. 15: the lines; 16: an alerted zone; 17: the labels' ink; 3 bytes each,
+ *              stored or blended as they are -- (Y, U, V) for _nv12, (B, G, R) for _bgr
+ *   alpha, alpha_occupied, alpha_alert: 0 .. 256, the weight of a zone's colour in its fill by the zone's state
+ *   outline    0 .. 32 px: a zone's edges as capsules of radius 2 outline quarter pixels (0: none)
+ *   thickness  1 .. 32 px: a line's capsule, radius 2 thickness;  arrow 0 .. 255 px: the length of its direction stem
+ *   label_scale  g in 0 .. 8: a font pixel is g x g picture pixels; 0: no labels
+ *   zone_label PAVE_ZONE_LABEL_NONE | _OCCUPANCY | _ENTERED;  line_label PAVE_LINE_LABEL_NONE | _NET | _FORWARD | _BACKWARD
+ *   font[d]    the 5 x 7 faces of the digits 0 .. 9 and, d = 10, of the minus sign: 7 rows, bit 4 the left-most pixel
+ * Pixel (px, py) is tinted by zone z iff the point (8 px, 8 py) is inside it by pave_zone_events' own test:
+ * out = (src (256 - a) + col a + 128) >> 8 per byte, zones in ascending index; an NV12 chroma sample once per zone
+ * with a_c = (a n + 2) >> 2 for its n luma pixels inside.  Over the fills lie opaque primitives, the largest id
+ * winning as in pave_draw_plan, on quarter-pixel vertices Q = G >> 1: zone edges (id 16 z + e), lines (128 + l),
+ * stems (136 + l), zone plates and their ink (144 + 2 z, + 1), line plates and their ink (160 + 2 l, + 1).  No byte
+ * that neither a fill with a positive alpha nor a primitive covers is written.
+ * Refused with PAVE_E_ARG before any device call: a null plan, surface or monitor tensor, n outside 1 .. 32, width or
+ * height outside 1 .. 8192, odd NV12 sizes, a pitch below a row's bytes, a table index >= 4, cameras outside
+ * 1 .. 4096, a camera outside [0, cameras), S outside 1 .. 128, an alpha outside 0 .. 256, outline outside 0 .. 32,
+ * thickness outside 1 .. 32, arrow outside 0 .. 255, label_scale outside 0 .. 8, zone_label outside 0 .. 2, line_label
+ * outside 0 .. 3, a font row with bits above the low 5.  A plan that passes cannot address memory outside its
+ * tensors, whatever the geometry, the counters and the state hold.
+ */
+#define PAVE_ZONE_DRAW_COLORS 18
+#define PAVE_ZONE_DRAW_ALERT 16
+#define PAVE_ZONE_DRAW_INK 17
+#define PAVE_ZONE_DRAW_FACES 11
+#define PAVE_ZONE_LABEL_NONE 0
+#define PAVE_ZONE_LABEL_OCCUPANCY 1
+#define PAVE_ZONE_LABEL_ENTERED 2
+#define PAVE_LINE_LABEL_NONE 0
+#define PAVE_LINE_LABEL_NET 1
+#define PAVE_LINE_LABEL_FORWARD 2
+#define PAVE_LINE_LABEL_BACKWARD 3
+typedef struct pave_zone_draw_plan {
+  void*          dst[PAVE_DRAW_MAX_SURFACES];
+  int            pitch[PAVE_DRAW_MAX_SURFACES];
+  int            width[PAVE_DRAW_MAX_SURFACES];
+  int            height[PAVE_DRAW_MAX_SURFACES];
+  int            camera[PAVE_DRAW_MAX_SURFACES];
+  uint8_t        table[PAVE_DRAW_MAX_SURFACES];
+  const int32_t* geometry;
+  const int32_t* counters;
+  const int32_t* slot_id;
+  const int32_t* slot_alerted;
+  const int32_t* slot_inside;
+  uint8_t        color[PAVE_DRAW_MAX_TABLES][PAVE_ZONE_DRAW_COLORS][3];
+  uint8_t        font[PAVE_ZONE_DRAW_FACES][7];
+  int n, cameras, S, alpha, alpha_occupied, alpha_alert, outline, thickness, arrow, label_scale, zone_label, line_label;
+} pave_zone_draw_plan;
+int pave_draw_zones_nv12(const pave_zone_draw_plan* plan, void* stream);
+int pave_draw_zones_bgr(const pave_zone_draw_plan* plan, void* stream);
+
+/*
  * The same person again: a colour descriptor per pose read from the pixels under it, and a gallery per camera that
  * maps track ids to person ids which survive a gap (pavenet_amd/csrc/pave_reid.hip; the rule is DESIGN section 18,
  * integer-exact).  The plans are copied into the kernels' arguments; the surfaces are read only.

@@ -219,6 +219,25 @@ class ZonePlan(ctypes.Structure):
                 ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
 
 
+ZONE_DRAW_COLORS, ZONE_DRAW_ALERT, ZONE_DRAW_INK, ZONE_DRAW_FACES = (
+    DEFINES['PAVE_ZONE_DRAW_' + n] for n in ('COLORS', 'ALERT', 'INK', 'FACES'))
+
+
+class ZoneDrawPlan(ctypes.Structure):
+    """`pave_zone_draw_plan` of include/pave_hip.h (the by-value argument of pave_draw_zones_nv12 / _bgr)."""
+    _fields_ = [('dst', ctypes.c_void_p * DRAW_MAX_SURFACES), ('pitch', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('width', ctypes.c_int * DRAW_MAX_SURFACES), ('height', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('camera', ctypes.c_int * DRAW_MAX_SURFACES), ('table', ctypes.c_uint8 * DRAW_MAX_SURFACES),
+                ('geometry', ctypes.c_void_p), ('counters', ctypes.c_void_p), ('slot_id', ctypes.c_void_p),
+                ('slot_alerted', ctypes.c_void_p), ('slot_inside', ctypes.c_void_p),
+                ('color', ((ctypes.c_uint8 * 3) * ZONE_DRAW_COLORS) * DRAW_MAX_TABLES),
+                ('font', (ctypes.c_uint8 * 7) * ZONE_DRAW_FACES), ('n', ctypes.c_int), ('cameras', ctypes.c_int),
+                ('S', ctypes.c_int), ('alpha', ctypes.c_int), ('alpha_occupied', ctypes.c_int),
+                ('alpha_alert', ctypes.c_int), ('outline', ctypes.c_int), ('thickness', ctypes.c_int),
+                ('arrow', ctypes.c_int), ('label_scale', ctypes.c_int), ('zone_label', ctypes.c_int),
+                ('line_label', ctypes.c_int)]
+
+
 REID_BINS, REID_CAP, REID_MIN_SAMPLES, REID_MAX_PART, REID_MAX_HITS, REID_NEVER = (
     DEFINES['PAVE_REID_' + n] for n in ('BINS', 'CAP', 'MIN_SAMPLES', 'MAX_PART', 'MAX_HITS', 'NEVER'))
 

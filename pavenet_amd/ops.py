@@ -17,6 +17,7 @@ is no CPU path: a non-device tensor raises, exactly as the reference's
 """
 import contextlib
 import ctypes
+import numbers
 
 import torch
 
@@ -1101,6 +1102,128 @@ def zone_events(entries, state, *, K, max_age=30, anchor='feet', anchor_kpts=(),
         plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
         _launch('pave_zone_events', who, dev, ctypes.byref(plan))
     return outs
+
+
+ZONE_LABELS = ('none', 'occupancy', 'entered')              # PAVE_ZONE_LABEL_*
+LINE_LABELS = ('none', 'net', 'forward', 'backward')        # PAVE_LINE_LABEL_*
+_ZONE_DRAW_STATE = (('geometry', native.ZONE_GEOM_WORDS), ('counters', native.ZONE_COUNTER_WORDS), ('id', 0),
+                    ('alerted', 0), ('inside', 0))           # name, columns (0: S)
+
+
+def draw_zones(kind, items, state, tables, font, *, alpha=48, alpha_occupied=96, alpha_alert=128, outline=2,
+               thickness=3, arrow=24, label_scale=2, zone_label='occupancy', line_label='net'):
+    """Zones, counting lines and their counts drawn into surfaces in place, one launch per 32 surfaces
+    (pave_draw_zones_nv12 / _bgr; the rule is DESIGN section 19).  kind 'nv12' | 'bgr' as in draw_poses.  items: one
+    (surface, width, camera, table) per surface (`width` is not read for 'bgr'; a 'bgr' surface may be the rows of a
+    wider buffer: strides (pitch, 3, 1)).  state: the monitor's int32 device
+    tensors geometry [cameras, 306], counters [cameras, 56] and id, alerted, inside [cameras, S], read only.  tables:
+    1 .. 4 of 18 x 3 bytes stored or blended as they are (rows 0 .. 7 zones, 8 .. 15 lines, 16 an alerted zone, 17 the
+    ink; nested or as the 54 bytes); font: 11 faces (the digits and a minus) of 7 rows of 5 bits.  The alphas 0 .. 256,
+    outline 0 .. 32, thickness 1 .. 32, arrow 0 .. 255, label_scale 0 .. 8, zone_label 'occupancy' | 'entered' | 'none',
+    line_label 'net' | 'forward' | 'backward' | 'none'.  Shapes, types and ranges raise ValueError before anything is
+    asked of a device."""
+    who = 'draw_zones'
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
+    items = list(items)
+    if not items:
+        raise ValueError(f'{who}: no surface')
+    if any(not (isinstance(it, (tuple, list)) and len(it) == 4) for it in items):
+        raise ValueError(f'{who}: an item is (surface, width, camera, table)')
+    for name, v, lo, hi in (('alpha', alpha, 0, 256), ('alpha_occupied', alpha_occupied, 0, 256),
+                            ('alpha_alert', alpha_alert, 0, 256), ('outline', outline, 0, 32),
+                            ('thickness', thickness, 1, 32), ('arrow', arrow, 0, 255), ('label_scale', label_scale, 0, 8)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} is an integer in {lo} .. {hi}, got {v!r}')
+    if zone_label not in ZONE_LABELS:
+        raise ValueError(f'{who}: zone_label is one of {", ".join(ZONE_LABELS)}, got {zone_label!r}')
+    if line_label not in LINE_LABELS:
+        raise ValueError(f'{who}: line_label is one of {", ".join(LINE_LABELS)}, got {line_label!r}')
+    try:
+        font = [[int(r) for r in rows] for rows in font]
+    except (TypeError, ValueError):
+        font = []
+    if len(font) != native.ZONE_DRAW_FACES or any(len(rows) != 7 or any(not 0 <= r < 32 for r in rows) for rows in font):
+        raise ValueError(f'{who}: font is {native.ZONE_DRAW_FACES} faces of 7 rows of 5 bits')
+    try:
+        tables = [tab if isinstance(tab, bytes) else bytes(int(c) for row in tab for c in (row if len(row) == 3 else ()))
+                  for tab in tables]
+    except (TypeError, ValueError):
+        tables = []
+    if not 1 <= len(tables) <= native.DRAW_MAX_TABLES or any(len(t) != 3 * native.ZONE_DRAW_COLORS for t in tables):
+        raise ValueError(f'{who}: tables are 1 .. {native.DRAW_MAX_TABLES} of {native.ZONE_DRAW_COLORS} x 3 bytes')
+    if not isinstance(state, dict) or any(not isinstance(state.get(n), torch.Tensor) for n, _ in _ZONE_DRAW_STATE):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(n for n, _ in _ZONE_DRAW_STATE)}')
+    if state['id'].dim() != 2:
+        raise ValueError(f'{who}: state id must be [cameras, S], got {tuple(state["id"].shape)}')
+    cameras, S = state['id'].shape
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS} and S in 1 .. {native.TRACK_MAX_TRACKS}, got '
+                         f'{cameras} and {S}')
+    for name, columns in _ZONE_DRAW_STATE:
+        t, want = state[name], (cameras, columns or S)
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    geometry = []
+    for i, (surf, width, camera, table) in enumerate(items):
+        if not (isinstance(surf, torch.Tensor) and surf.dtype == torch.uint8):
+            raise ValueError(f'{who}: surface {i} must be a uint8 tensor')
+        if kind == 'nv12':
+            if surf.dim() != 2:
+                raise ValueError(f'{who}: surface {i} must be [H * 3 // 2, pitch], got {tuple(surf.shape)}')
+            if isinstance(width, bool) or not isinstance(width, numbers.Integral):
+                raise ValueError(f'{who}: the width of surface {i} must be an integer, got {width!r}')
+            rows, pitch = surf.shape
+            H, W, row_bytes = rows * 2 // 3, int(width), int(width)
+            if rows % 3 != 0 or H % 2 != 0 or H <= 0:
+                raise ValueError(f'{who}: surface {i}: {rows} rows are not the 3/2 of an even height')
+            if W <= 0 or W % 2 != 0:
+                raise ValueError(f'{who}: surface {i}: width {W} must be even and positive')
+        else:
+            if surf.dim() != 3 or surf.shape[2] != 3 or surf.shape[0] < 1 or surf.shape[1] < 1:
+                raise ValueError(f'{who}: surface {i} must be [H, W, 3], got {tuple(surf.shape)}')
+            H, W = surf.shape[:2]
+            row_bytes = 3 * W
+            pitch = row_bytes if surf.is_contiguous() else surf.stride(0)     # (rows of a wider buffer)
+            if not surf.is_contiguous() and (surf.stride(2) != 1 or surf.stride(1) != 3):
+                raise ValueError(f'{who}: surface {i} must be contiguous, or contiguous rows of a wider buffer')
+        if row_bytes > pitch:
+            raise ValueError(f'{who}: surface {i}: width {W} exceeds the pitch {pitch}')
+        if W > native.DRAW_MAX_SIZE or H > native.DRAW_MAX_SIZE:
+            raise ValueError(f'{who}: surface {i}: {W} x {H} exceeds {native.DRAW_MAX_SIZE} x {native.DRAW_MAX_SIZE}')
+        if kind == 'nv12' and not surf.is_contiguous():
+            raise ValueError(f'{who}: surface {i} must be contiguous')
+        if isinstance(camera, bool) or not isinstance(camera, numbers.Integral) or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of surface {i} must be an integer in [0, {cameras}), got {camera!r}')
+        if isinstance(table, bool) or not isinstance(table, numbers.Integral) or not 0 <= table < len(tables):
+            raise ValueError(f'{who}: surface {i} names colour table {table} of {len(tables)}')
+        geometry.append((int(pitch), int(W), int(H), int(camera), int(table)))
+    # the shapes are right: now where the tensors live
+    dev = state['id'].device
+    if dev.type != 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n, _ in _ZONE_DRAW_STATE):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, it in enumerate(items):
+        if it[0].device != dev:
+            raise ValueError(f"{who}: surface {i} is on {it[0].device}, the monitor's state on {dev}")
+    entry = 'pave_draw_zones_nv12' if kind == 'nv12' else 'pave_draw_zones_bgr'
+    raw_tables, raw_font = b''.join(tables), bytes(r for rows in font for r in rows)
+    for at in range(0, len(items), native.DRAW_MAX_SURFACES):
+        plan = native.ZoneDrawPlan()
+        part = items[at:at + native.DRAW_MAX_SURFACES]
+        for i, it in enumerate(part):
+            plan.dst[i] = it[0].data_ptr()
+            plan.pitch[i], plan.width[i], plan.height[i], plan.camera[i], plan.table[i] = geometry[at + i]
+        plan.geometry, plan.counters, plan.slot_id, plan.slot_alerted, plan.slot_inside = (
+            state[n].data_ptr() for n, _ in _ZONE_DRAW_STATE)
+        ctypes.memmove(plan.color, raw_tables, len(raw_tables))
+        ctypes.memmove(plan.font, raw_font, len(raw_font))
+        plan.n, plan.cameras, plan.S = len(part), cameras, S
+        plan.alpha, plan.alpha_occupied, plan.alpha_alert = alpha, alpha_occupied, alpha_alert
+        plan.outline, plan.thickness, plan.arrow, plan.label_scale = outline, thickness, arrow, label_scale
+        plan.zone_label, plan.line_label = ZONE_LABELS.index(zone_label), LINE_LABELS.index(line_label)
+        _launch(entry, who, dev, ctypes.byref(plan))
 
 
 _REID_STATE = (('person', 1), ('track', 1), ('last', 1), ('hits', 2), ('hist', 3), ('frame', 0), ('next', 0),

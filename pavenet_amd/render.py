@@ -5,8 +5,8 @@ reference's public method on top of the latter (opera/models/detectors/videopose
 the host there).  Drawing is in place, one launch per 32 surfaces, and reads no device value on the host: the
 fixed-shape ``dict(bboxes=, kpts=, keep=)`` of ``head.get_bboxes`` is drawn without the sync of ``results_to_list``.
 
-Hard-edged integer coverage (no anti-aliasing, no blending; the only text is the digits of a track id).  With
-``ids=`` (what ``PoseTracker.update`` returns, still on the device) a tracked pose takes a colour chosen by its id and
+Hard-edged integer coverage (no anti-aliasing, no blending; the only text is the digits of a track id; zones, lines
+and their counts are ``overlay.py``'s).  With ``ids=`` (what ``PoseTracker.update`` returns, still on the device) a tracked pose takes a colour chosen by its id and
 a small plate with the id above its box (``TrackStyle``).  Skeletons are written from the key-point
 orders of ``keypoints.py`` (PoseTrack: nose, head bottom, head top, then left / right shoulder, elbow, wrist, hip,
 knee, ankle); the palette is this project's: left limbs warm, right limbs cool, the middle green.
@@ -49,6 +49,9 @@ DIGIT_FONT = tuple(tuple(int(row.replace('.', '0').replace('#', '1'), 2) for row
     '##### ....# ...#. ..#.. .#... .#... .#...',
     '.###. #...# #...# .###. #...# #...# .###.',
     '.###. #...# #...# .#### ....# ...#. .##..'))
+# The 11th face, for counts that can be negative (overlay.py: a line's forward - backward): same cell, same encoding.
+MINUS_FACE = tuple(int(row.replace('.', '0').replace('#', '1'), 2) for row in
+                   '..... ..... ..... ##### ..... ..... .....'.split())
 
 
 def _builtin(K):

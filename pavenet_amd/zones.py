@@ -9,8 +9,9 @@ Count on the raw result where latency matters and on the smoothed one where flic
 not debounced: a track that jitters on a line crosses it forward and backward, and forward - backward is the robust
 figure.
 
-Not built: drawing zones or counters into the picture, a hysteresis band for lines, zones in ground-plane
-coordinates, per-id exemptions in ``anonymize``.
+``overlay.draw_zones_nv12`` / ``draw_zones_bgr`` draw the zones, the lines and these counters into the picture.
+
+Not built: a hysteresis band for lines, zones in ground-plane coordinates, per-id exemptions in ``anonymize``.
 """
 import math
 
@@ -228,6 +229,14 @@ class ZoneMonitor:
         if self._state is None:
             return None
         return {name: self._state[name][camera] for name in _STATE}
+
+    def device_tensors(self):
+        """The whole tensors a reader on the device needs, for every camera at once and read only: geometry
+        [cameras, 306], counters [cameras, 56] and id, alerted, inside [cameras, S] (what `overlay.draw_zones_*`
+        hands to its kernel).  None before the first call."""
+        if self._state is None:
+            return None
+        return {name: self._state[name] for name in ('geometry', 'counters', 'id', 'alerted', 'inside')}
 
     def geometry(self, camera=0):
         """Views of one camera's geometry on the device, in 1/8 pixel: n_zones, n_lines (0-d), n_vertices,
