@@ -889,6 +889,108 @@ int pave_reid_update_nv12(const pave_reid_plan* plan, void* stream);
 int pave_reid_update_bgr(const pave_reid_plan* plan, void* stream);
 
 /*
+ * Postures and falls: the class of every tracked pose from its trunk and legs, debounced per track id, with the
+ * posture changes, falls, people who stay down and raised hands of the frame (pavenet_amd/csrc/pave_posture.hip; the
+ * rule is DESIGN section 20, integer-exact), one launch for `entries` frames of any of `cameras` cameras.  The plan is
+ * copied into the kernel's arguments.  One block per camera of the launch takes that camera's entries in plan order:
+ * entries of one camera are in time order.
+ *   kpts[i], bboxes[i], keep[i], n[i], camera[i], scale[i]   as in pave_track_plan;  ids[i] as in pave_smooth_plan
+ *   out_posture[i]   DEVICE [n[i]] int32, out: the debounced posture of the pose's track, PAVE_POSTURE_UNKNOWN ..
+ *                    _LYING, or -1 where the pose takes no part
+ *   out_raw[i]       DEVICE [n[i]] int32, out: the class of this frame alone, or -1
+ *   out_hands[i]     DEVICE [n[i]] int32, out: bit w set iff wrist w of the part `wrists` is raised in this frame
+ *   out_since[i]     DEVICE [n[i]] int32, out: the frames the track has spent in its posture (0: takes no part)
+ *   out_events[i]    DEVICE [max_events, 5] int32, out: the frame's events (kind, index, id, pose, frame) in the
+ *                    rule's fixed order, the first max_events of them; rows past the count are zero.  index: the new
+ *                    class (POSTURE), frame - upright (FALL), the frames lying (DOWN), the raw wrist mask (HANDS_*)
+ *   out_n_events[i]  DEVICE [1] int32, out: ALL events of the frame (it may exceed max_events)
+ *                    out_posture, out_raw, out_hands and out_since may be NULL where n[i] == 0 (the frame still counts)
+ *   the state, DEVICE int32, read and written: slot_id, slot_last, slot_posture, slot_since, slot_upright (the last
+ *                    frame the slot was seen UPRIGHT, 0: never), slot_streak, slot_alerted, slot_hands (0 | 1),
+ *                    slot_hand_streak [cameras, S] (id 0: a free slot, its other fields are never read); frame,
+ *                    dropped [cameras]; counters [cameras, PAVE_POSTURE_COUNTER_WORDS]: the live slots per posture
+ *                    [5] at PAVE_POSTURE_CNT_NOW, the live slots with a raised hand, and the running totals of falls
+ *                    and of DOWN events
+ *   part[p][0 .. n_part[p])   the key points of part p = PAVE_POSTURE_PART_SHOULDERS | _HIPS | _ANKLES | _WRISTS.
+ *                    n_part is clamped to 0 .. 4 and an index to [0, K) as they are read
+ *   min_frames       1 .. 255: the frames a raw class (a raw hand bit) must disagree before the posture (the bit) follows
+ *   lean, flat       1 .. 255, sixteenths of a slope: UPRIGHT up to |dx| / dy = lean / 16, LYING up to |dy| / |dx| = flat / 16
+ *   squat            0 .. 255, sixteenths of the trunk's height: LOW iff the ankles are less than that below the hips
+ *                    (0: no LOW)
+ *   hand_up          PAVE_POSTURE_HANDS_OFF, or 0 .. 255, sixteenths of the trunk's height a wrist is above the shoulders
+ *   fall_window      0 .. 2^30: LYING within so many frames of UPRIGHT is a FALL
+ *   down_frames      0 .. 2^30: the frames lying after which DOWN is reported once (0: never)
+ * Refused with PAVE_E_ARG before any device call: whatever pave_zone_events refuses in the fields of the same name (a
+ * null plan or state tensor, a null kpts, bboxes or ids where n[i] > 0, entries outside 1 .. 32, n[i] outside
+ * 0 .. 128, K outside 1 .. 32, S outside 1 .. 128, cameras outside 1 .. 4096, a camera index outside [0, cameras), a
+ * scale that is not positive and finite, max_age < 0, a null counters tensor, a null out_events or out_n_events,
+ * min_frames outside 1 .. 255, max_events outside 1 .. 4096), a null out_posture, out_raw, out_hands or out_since
+ * where n[i] > 0, lean or flat outside 1 .. 255, squat outside 0 .. 255, hand_up outside -1 .. 255, fall_window or
+ * down_frames outside 0 .. 2^30, an n_part outside 0 .. 4, a part index outside [0, K).  Every loop bound is from the
+ * plan or the maxima below: a plan that passes cannot address memory outside its tensors, whatever the poses, the ids
+ * and the stored state hold.
+ */
+#define PAVE_POSTURE_UNKNOWN 0
+#define PAVE_POSTURE_UPRIGHT 1
+#define PAVE_POSTURE_LOW 2
+#define PAVE_POSTURE_LEANING 3
+#define PAVE_POSTURE_LYING 4
+#define PAVE_POSTURE_CLASSES 5
+#define PAVE_POSTURE_EV_POSTURE 1
+#define PAVE_POSTURE_EV_FALL 2
+#define PAVE_POSTURE_EV_DOWN 3
+#define PAVE_POSTURE_EV_HANDS_UP 4
+#define PAVE_POSTURE_EV_HANDS_DOWN 5
+#define PAVE_POSTURE_PART_SHOULDERS 0
+#define PAVE_POSTURE_PART_HIPS 1
+#define PAVE_POSTURE_PART_ANKLES 2
+#define PAVE_POSTURE_PART_WRISTS 3
+#define PAVE_POSTURE_PARTS 4
+#define PAVE_POSTURE_MAX_PART 4
+#define PAVE_POSTURE_MAX_EVENTS 4096
+#define PAVE_POSTURE_EVENT_WORDS 5
+#define PAVE_POSTURE_MAX_SLOPE 255
+#define PAVE_POSTURE_MAX_WAIT 1073741824
+#define PAVE_POSTURE_HANDS_OFF (-1)
+#define PAVE_POSTURE_CNT_NOW 0
+#define PAVE_POSTURE_CNT_HANDS_UP 5
+#define PAVE_POSTURE_CNT_FALLS 6
+#define PAVE_POSTURE_CNT_DOWNS 7
+#define PAVE_POSTURE_COUNTER_WORDS 8
+typedef struct pave_posture_plan {
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_posture[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_raw[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_hands[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_since[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_events[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_n_events[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int32_t* slot_id;
+  int32_t* slot_last;
+  int32_t* slot_posture;
+  int32_t* slot_since;
+  int32_t* slot_upright;
+  int32_t* slot_streak;
+  int32_t* slot_alerted;
+  int32_t* slot_hands;
+  int32_t* slot_hand_streak;
+  int32_t* frame;
+  int32_t* dropped;
+  int32_t* counters;
+  int part[PAVE_POSTURE_PARTS][PAVE_POSTURE_MAX_PART];
+  int n_part[PAVE_POSTURE_PARTS];
+  int entries, cameras, S, K, min_frames, lean, flat, squat, hand_up, fall_window, down_frames, max_events, max_age;
+  float score_thr, kpt_thr;
+} pave_posture_plan;
+int pave_posture_events(const pave_posture_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

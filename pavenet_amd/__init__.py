@@ -47,6 +47,9 @@ def __getattr__(name):
     if name == 'ZoneMonitor':
         from . import zones
         return zones.ZoneMonitor
+    if name == 'PostureMonitor':
+        from . import posture
+        return posture.PostureMonitor
     if name in ('ZoneStyle', 'draw_zones_nv12', 'draw_zones_bgr'):
         from . import overlay
         return getattr(overlay, name)

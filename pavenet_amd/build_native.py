@@ -25,6 +25,7 @@ SOURCES = [os.path.join(_HERE, 'csrc', 'pave_kernels.hip'),
            os.path.join(_HERE, 'csrc', 'pave_track.hip'),
            os.path.join(_HERE, 'csrc', 'pave_smooth.hip'),
            os.path.join(_HERE, 'csrc', 'pave_zones.hip'),
+           os.path.join(_HERE, 'csrc', 'pave_posture.hip'),
            os.path.join(_HERE, 'csrc', 'pave_overlay.hip'),
            os.path.join(_HERE, 'csrc', 'pave_reid.hip'),
            os.path.join(_HERE, 'csrc', 'pave_anon.hip')]

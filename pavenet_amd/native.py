@@ -266,6 +266,33 @@ class ReidPlan(ctypes.Structure):
                 ('match_thr', ctypes.c_int), ('min_hits', ctypes.c_int), ('gain', ctypes.c_int)]
 
 
+POSTURE_CLASSES, POSTURE_PARTS, POSTURE_MAX_PART, POSTURE_MAX_EVENTS, POSTURE_EVENT_WORDS, POSTURE_COUNTER_WORDS = (
+    DEFINES['PAVE_POSTURE_' + n] for n in ('CLASSES', 'PARTS', 'MAX_PART', 'MAX_EVENTS', 'EVENT_WORDS', 'COUNTER_WORDS'))
+POSTURE_MAX_SLOPE, POSTURE_MAX_WAIT, POSTURE_HANDS_OFF = (
+    DEFINES['PAVE_POSTURE_' + n] for n in ('MAX_SLOPE', 'MAX_WAIT', 'HANDS_OFF'))
+
+
+class PosturePlan(ctypes.Structure):
+    """`pave_posture_plan` of include/pave_hip.h (the by-value argument of pave_posture_events)."""
+    _fields_ = [('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_posture', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_raw', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_hands', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_since', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_events', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_n_events', ctypes.c_void_p * TRACK_MAX_FRAMES), ('n', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('camera', ctypes.c_int * TRACK_MAX_FRAMES), ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES),
+                ('slot_id', ctypes.c_void_p), ('slot_last', ctypes.c_void_p), ('slot_posture', ctypes.c_void_p),
+                ('slot_since', ctypes.c_void_p), ('slot_upright', ctypes.c_void_p), ('slot_streak', ctypes.c_void_p),
+                ('slot_alerted', ctypes.c_void_p), ('slot_hands', ctypes.c_void_p),
+                ('slot_hand_streak', ctypes.c_void_p), ('frame', ctypes.c_void_p), ('dropped', ctypes.c_void_p),
+                ('counters', ctypes.c_void_p), ('part', (ctypes.c_int * POSTURE_MAX_PART) * POSTURE_PARTS),
+                ('n_part', ctypes.c_int * POSTURE_PARTS), ('entries', ctypes.c_int), ('cameras', ctypes.c_int),
+                ('S', ctypes.c_int), ('K', ctypes.c_int), ('min_frames', ctypes.c_int), ('lean', ctypes.c_int),
+                ('flat', ctypes.c_int), ('squat', ctypes.c_int), ('hand_up', ctypes.c_int),
+                ('fall_window', ctypes.c_int), ('down_frames', ctypes.c_int), ('max_events', ctypes.c_int),
+                ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
+
+
 _lib = None
 
 

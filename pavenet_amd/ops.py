@@ -1104,6 +1104,132 @@ def zone_events(entries, state, *, K, max_age=30, anchor='feet', anchor_kpts=(),
     return outs
 
 
+_POSTURE_STATE = (('id', 1), ('last', 1), ('posture', 1), ('since', 1), ('upright', 1), ('streak', 1), ('alerted', 1),
+                  ('hands', 1), ('hand_streak', 1), ('frame', 0), ('dropped', 0), ('counters', 2))
+# name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, 8]
+POSTURE_PARTS = ('shoulders', 'hips', 'ankles', 'wrists')   # PAVE_POSTURE_PART_*
+
+
+def posture_events(entries, state, *, K, parts, max_age=30, min_frames=3, lean=11, flat=11, squat=18, hand_up=4,
+                   fall_window=30, down_frames=75, max_events=256, score_thr=0.3, kpt_thr=0.):
+    """Postures, falls and raised hands for frames of tracked poses, one launch per 32 frames (pave_posture_events;
+    the rule is DESIGN section 20).  entries: one (kpts [N, K, 3] fp32, bboxes [N, 5] fp32, keep [N] int32 or None, ids
+    [N] int32, camera, (sx, sy)) per frame, N <= 128, the frames of one camera in time order; state: int32 device
+    tensors id, last, posture, since, upright, streak, alerted, hands, hand_streak [cameras, S], frame, dropped
+    [cameras] and counters [cameras, 8] (PAVE_POSTURE_CNT_* of include/pave_hip.h), read and written; parts: four
+    lists of at most 4 key points in [0, K), the shoulders, hips, ankles and wrists; min_frames 1 .. 255, lean and
+    flat 1 .. 255, squat 0 .. 255, hand_up 0 .. 255 or None, fall_window and down_frames 0 .. 2^30, max_events
+    1 .. 4096.  Returns one dict(posture, raw, hands, since [N], events [max_events, 5], n_events 0-d) of new int32
+    tensors per entry.  Shapes, types and ranges raise ValueError before anything is asked of a device."""
+    who = 'posture_events'
+    entries = list(entries)
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name, _ in _POSTURE_STATE):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(n for n, _ in _POSTURE_STATE)}')
+    if state['id'].dim() != 2:
+        raise ValueError(f'{who}: state id must be [cameras, S], got {tuple(state["id"].shape)}')
+    cameras, S = state['id'].shape
+    if isinstance(K, bool) or not isinstance(K, int):
+        raise ValueError(f'{who}: K must be an integer, got {K!r}')
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS
+            and 1 <= K <= native.TRACK_MAX_K):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS}, S in 1 .. {native.TRACK_MAX_TRACKS} and K '
+                         f'in 1 .. {native.TRACK_MAX_K}, got {cameras}, {S} and {K}')
+    dev = state['id'].device
+    for name, kind in _POSTURE_STATE:
+        t = state[name]
+        want = ((cameras,), (cameras, S), (cameras, native.POSTURE_COUNTER_WORDS))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    for name, v, lo, hi in (('min_frames', min_frames, 1, 255), ('max_events', max_events, 1, native.POSTURE_MAX_EVENTS),
+                            ('lean', lean, 1, native.POSTURE_MAX_SLOPE), ('flat', flat, 1, native.POSTURE_MAX_SLOPE),
+                            ('squat', squat, 0, native.POSTURE_MAX_SLOPE),
+                            ('hand_up', 0 if hand_up is None else hand_up, 0, native.POSTURE_MAX_SLOPE),
+                            ('fall_window', fall_window, 0, native.POSTURE_MAX_WAIT),
+                            ('down_frames', down_frames, 0, native.POSTURE_MAX_WAIT)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    try:
+        parts = [list(p) for p in parts]
+    except TypeError:
+        raise ValueError(f'{who}: parts are the key points of {", ".join(POSTURE_PARTS)}') from None
+    if len(parts) != native.POSTURE_PARTS:
+        raise ValueError(f'{who}: parts are the key points of {", ".join(POSTURE_PARTS)}, got {len(parts)} lists')
+    for name, p in zip(POSTURE_PARTS, parts):
+        if len(p) > native.POSTURE_MAX_PART or any(
+                isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in p):
+            raise ValueError(f'{who}: part {name} holds at most {native.POSTURE_MAX_PART} integers in [0, {K}), got '
+                             f'{p!r}')
+    checked = []
+    for i, entry in enumerate(entries):
+        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
+            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
+        kpts, bboxes, keep, ids, camera, scale = entry
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
+            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
+        if N > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+        try:
+            sx, sy = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
+        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
+        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    # the shapes are right: now where the tensors live
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n, _ in _POSTURE_STATE):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if any(t is not None and t.device != dev for t in c[:4]):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    z = dict(dtype=torch.int32, device=dev)
+    outs = [dict(posture=torch.empty((c[7],), **z), raw=torch.empty((c[7],), **z), hands=torch.empty((c[7],), **z),
+                 since=torch.empty((c[7],), **z), events=torch.empty((max_events, native.POSTURE_EVENT_WORDS), **z),
+                 n_events=torch.empty((), **z)) for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.PosturePlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
+            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+                _ptr(keep) or None, _ptr(ids) or None
+            out = outs[at + i]
+            plan.out_posture[i], plan.out_raw[i] = out['posture'].data_ptr() or None, out['raw'].data_ptr() or None
+            plan.out_hands[i], plan.out_since[i] = out['hands'].data_ptr() or None, out['since'].data_ptr() or None
+            plan.out_events[i], plan.out_n_events[i] = out['events'].data_ptr(), out['n_events'].data_ptr()
+            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+        (plan.slot_id, plan.slot_last, plan.slot_posture, plan.slot_since, plan.slot_upright, plan.slot_streak,
+         plan.slot_alerted, plan.slot_hands, plan.slot_hand_streak, plan.frame, plan.dropped, plan.counters) = (
+            state[n].data_ptr() for n, _ in _POSTURE_STATE)
+        for p, keys in enumerate(parts):
+            plan.n_part[p] = len(keys)
+            for i, k in enumerate(keys):
+                plan.part[p][i] = k
+        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
+        plan.min_frames, plan.lean, plan.flat, plan.squat = min_frames, lean, flat, squat
+        plan.hand_up = native.POSTURE_HANDS_OFF if hand_up is None else hand_up
+        plan.fall_window, plan.down_frames, plan.max_events, plan.max_age = fall_window, down_frames, max_events, \
+            int(max_age)
+        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        _launch('pave_posture_events', who, dev, ctypes.byref(plan))
+    return outs
+
+
 ZONE_LABELS = ('none', 'occupancy', 'entered')              # PAVE_ZONE_LABEL_*
 LINE_LABELS = ('none', 'net', 'forward', 'backward')        # PAVE_LINE_LABEL_*
 _ZONE_DRAW_STATE = (('geometry', native.ZONE_GEOM_WORDS), ('counters', native.ZONE_COUNTER_WORDS), ('id', 0),
