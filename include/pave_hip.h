@@ -991,6 +991,94 @@ typedef struct pave_posture_plan {
 int pave_posture_events(const pave_posture_plan* plan, void* stream);
 
 /*
+ * Footfall heat maps: where tracked people stood and walked, accumulated per camera on a grid of cells, and the map
+ * as a colour overlay (pavenet_amd/csrc/pave_heat.hip; the rules are DESIGN section 21, integer-exact).  The plans are
+ * copied into the kernels' arguments.
+ *
+ * pave_heat_update: one launch for `entries` frames of any of `cameras` cameras; one block per camera of the launch
+ * takes that camera's entries in plan order, as pave_zone_events does: entries of one camera are in time order.
+ *   kpts[i], bboxes[i], keep[i], ids[i], n[i], camera[i], scale[i], anchor, anchor_kpt, n_anchor, S, K, max_age,
+ *   score_thr, kpt_thr   as in pave_zone_plan: the same poses take part and stand on the same 1/8-pixel anchor
+ *   out_cell[i]      DEVICE [n[i]] int32, out: the pose's cell gy Gw + gx, -1 if it takes no part or is off the map
+ *   out_dwell[i], out_visits[i]   DEVICE [n[i]] int32, out: the two maps at that cell after the frame, else 0
+ *                    (all three may be NULL where n[i] == 0: the frame still counts)
+ *   the state, DEVICE int32, read and written: slot_id, slot_last, slot_cell [cameras, S] (id 0: a free slot, its
+ *                    other fields are never read; cell -1: off the map); frame, dropped [cameras]; peak [cameras, 2]
+ *                    (the maxima of dwell and visits); dwell, visits [cameras, Gh, Gw], Gw = ceil(width / cell),
+ *                    Gh = ceil(height / cell)
+ *   width, height    the map's size in original-image pixels, 1 .. 8192; cell 4 | 8 | 16 | 32 | 64; Gw, Gh <= 512
+ *   radius           0 .. 3: a pose adds (r + 1 - |dx|)(r + 1 - |dy|) to the cells within r of its own
+ *   half_life        0 .. 2^18: every half_life frames both maps and peak are halved (0: never)
+ * Refused with PAVE_E_ARG before any device call: whatever pave_zone_events refuses in the fields of the same name, a
+ * null map, peak or output tensor, width or height outside 1 .. 8192, a cell that is not one of the five, a grid above
+ * 512 cells a side, radius outside 0 .. 3, half_life outside 0 .. 2^18.
+ *
+ * pave_draw_heat_nv12 / _bgr: one launch for n separately allocated surfaces, in place; the maps are only read.
+ *   dst, pitch, width, height, table, camera: as in pave_zone_draw_plan
+ *   map        DEVICE [cameras, Gh, Gw] int32: the map that is drawn;  peak: DEVICE [cameras, 2] int32;  source:
+ *              PAVE_HEAT_DWELL | PAVE_HEAT_VISITS, the word of peak that belongs to map
+ *   palette    DEVICE [tables, 256, 3] bytes, stored or blended as they are: (Y, U, V) for _nv12, (B, G, R) for _bgr
+ *   map_width, map_height, cell: the map's size and cell as in pave_heat_plan
+ *   full_scale 1 .. 2^31 - 1, or 0: max(peak[camera][source], 1), read by the kernel
+ *   alpha_max  0 .. 256;  floor 0 .. 255;  smooth 0 | 1
+ * level = min(255, 255 max(v, 0) / scale) per cell (int64), taken from the pixel's own cell or (smooth) bilinear
+ * between cell centres; a = level < floor ? 0 : (alpha_max level + 128) >> 8; out = (src (256 - a) + palette[level] a
+ * + 128) >> 8 per byte; an NV12 chroma sample once, from the level at its block's centre.  A byte with a == 0, a pixel
+ * at or beyond the map's size and padding are never written.
+ * Refused with PAVE_E_ARG before any device call: a null plan, surface, map, peak or palette, n outside 1 .. 32, width
+ * or height outside 1 .. 8192, odd NV12 sizes, a pitch below a row's bytes, tables outside 1 .. 8, a table index >=
+ * tables, cameras outside 1 .. 4096, a camera outside [0, cameras), a map size, cell or grid as above, source outside
+ * 0 .. 1, full_scale < 0, alpha_max outside 0 .. 256, floor outside 0 .. 255, smooth outside 0 .. 1.
+ * Every cell index is clamped to the grid where it is formed and peak is clamped to >= 1 where it is read: a plan that
+ * passes cannot address memory outside its tensors, whatever the poses, the state and the maps hold.
+ */
+#define PAVE_HEAT_MAX_GRID 512
+#define PAVE_HEAT_MAX_RADIUS 3
+#define PAVE_HEAT_MAX_HALF_LIFE 262144
+#define PAVE_HEAT_MAX_TABLES 8
+#define PAVE_HEAT_DWELL 0
+#define PAVE_HEAT_VISITS 1
+typedef struct pave_heat_plan {
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_cell[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_dwell[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_visits[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int32_t* slot_id;
+  int32_t* slot_last;
+  int32_t* slot_cell;
+  int32_t* frame;
+  int32_t* dropped;
+  int32_t* peak;
+  int32_t* dwell;
+  int32_t* visits;
+  int anchor_kpt[PAVE_ZONE_MAX_ANCHOR_KPTS];
+  int entries, cameras, S, K, anchor, n_anchor, width, height, cell, radius, half_life, max_age;
+  float score_thr, kpt_thr;
+} pave_heat_plan;
+int pave_heat_update(const pave_heat_plan* plan, void* stream);
+
+typedef struct pave_heat_draw_plan {
+  void*          dst[PAVE_DRAW_MAX_SURFACES];
+  int            pitch[PAVE_DRAW_MAX_SURFACES];
+  int            width[PAVE_DRAW_MAX_SURFACES];
+  int            height[PAVE_DRAW_MAX_SURFACES];
+  int            camera[PAVE_DRAW_MAX_SURFACES];
+  uint8_t        table[PAVE_DRAW_MAX_SURFACES];
+  const int32_t* map;
+  const int32_t* peak;
+  const uint8_t* palette;
+  int n, cameras, tables, map_width, map_height, cell, source, full_scale, alpha_max, floor, smooth;
+} pave_heat_draw_plan;
+int pave_draw_heat_nv12(const pave_heat_draw_plan* plan, void* stream);
+int pave_draw_heat_bgr(const pave_heat_draw_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

@@ -53,6 +53,9 @@ def __getattr__(name):
     if name in ('ZoneStyle', 'draw_zones_nv12', 'draw_zones_bgr'):
         from . import overlay
         return getattr(overlay, name)
+    if name in ('FootfallMap', 'HeatStyle', 'draw_heat_nv12', 'draw_heat_bgr'):
+        from . import heatmap
+        return getattr(heatmap, name)
     if name == 'PersonReID':
         from . import reid
         return reid.PersonReID

@@ -293,6 +293,39 @@ class PosturePlan(ctypes.Structure):
                 ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
 
 
+HEAT_MAX_GRID, HEAT_MAX_RADIUS, HEAT_MAX_HALF_LIFE, HEAT_MAX_TABLES = (
+    DEFINES['PAVE_HEAT_MAX_' + n] for n in ('GRID', 'RADIUS', 'HALF_LIFE', 'TABLES'))
+
+
+class HeatPlan(ctypes.Structure):
+    """`pave_heat_plan` of include/pave_hip.h (the by-value argument of pave_heat_update)."""
+    _fields_ = [('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_cell', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_dwell', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_visits', ctypes.c_void_p * TRACK_MAX_FRAMES), ('n', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('camera', ctypes.c_int * TRACK_MAX_FRAMES), ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES),
+                ('slot_id', ctypes.c_void_p), ('slot_last', ctypes.c_void_p), ('slot_cell', ctypes.c_void_p),
+                ('frame', ctypes.c_void_p), ('dropped', ctypes.c_void_p), ('peak', ctypes.c_void_p),
+                ('dwell', ctypes.c_void_p), ('visits', ctypes.c_void_p),
+                ('anchor_kpt', ctypes.c_int * ZONE_MAX_ANCHOR_KPTS), ('entries', ctypes.c_int),
+                ('cameras', ctypes.c_int), ('S', ctypes.c_int), ('K', ctypes.c_int), ('anchor', ctypes.c_int),
+                ('n_anchor', ctypes.c_int), ('width', ctypes.c_int), ('height', ctypes.c_int), ('cell', ctypes.c_int),
+                ('radius', ctypes.c_int), ('half_life', ctypes.c_int), ('max_age', ctypes.c_int),
+                ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
+
+
+class HeatDrawPlan(ctypes.Structure):
+    """`pave_heat_draw_plan` of include/pave_hip.h (the by-value argument of pave_draw_heat_nv12 / _bgr)."""
+    _fields_ = [('dst', ctypes.c_void_p * DRAW_MAX_SURFACES), ('pitch', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('width', ctypes.c_int * DRAW_MAX_SURFACES), ('height', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('camera', ctypes.c_int * DRAW_MAX_SURFACES), ('table', ctypes.c_uint8 * DRAW_MAX_SURFACES),
+                ('map', ctypes.c_void_p), ('peak', ctypes.c_void_p), ('palette', ctypes.c_void_p),
+                ('n', ctypes.c_int), ('cameras', ctypes.c_int), ('tables', ctypes.c_int), ('map_width', ctypes.c_int),
+                ('map_height', ctypes.c_int), ('cell', ctypes.c_int), ('source', ctypes.c_int),
+                ('full_scale', ctypes.c_int), ('alpha_max', ctypes.c_int), ('floor', ctypes.c_int),
+                ('smooth', ctypes.c_int)]
+
+
 _lib = None
 
 

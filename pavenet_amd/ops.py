@@ -1352,6 +1352,231 @@ def draw_zones(kind, items, state, tables, font, *, alpha=48, alpha_occupied=96,
         _launch(entry, who, dev, ctypes.byref(plan))
 
 
+_HEAT_STATE = (('id', 1), ('last', 1), ('cell', 1), ('frame', 0), ('dropped', 0), ('peak', 2), ('dwell', 3),
+               ('visits', 3))   # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, 2], 3 [cameras, Gh, Gw]
+HEAT_CELLS = (4, 8, 16, 32, 64)
+HEAT_SOURCES = ('dwell', 'visits')             # PAVE_HEAT_DWELL, PAVE_HEAT_VISITS
+
+
+def heat_grid(who, size, cell):
+    """The (Gw, Gh) of a map of `size` = (width, height) original-image pixels at `cell`, or the ValueError."""
+    try:
+        width, height = size
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: size is (width, height), got {size!r}') from None
+    for v in (width, height):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= v <= native.DRAW_MAX_SIZE:
+            raise ValueError(f'{who}: size is (width, height) in 1 .. {native.DRAW_MAX_SIZE} pixels, got {size!r}')
+    if isinstance(cell, bool) or cell not in HEAT_CELLS:
+        raise ValueError(f'{who}: cell is one of {", ".join(str(c) for c in HEAT_CELLS)}, got {cell!r}')
+    Gw, Gh = -(-int(width) // cell), -(-int(height) // cell)
+    if Gw > native.HEAT_MAX_GRID or Gh > native.HEAT_MAX_GRID:
+        raise ValueError(f'{who}: the grid is at most {native.HEAT_MAX_GRID} cells a side, {size!r} at cell {cell} gives '
+                         f'{Gw} x {Gh}')
+    return Gw, Gh
+
+
+def _heat_state(who, state, names, size, cell):
+    """The shapes of the monitor's tensors `names` of _HEAT_STATE -> (cameras, S, Gw, Gh)."""
+    Gw, Gh = heat_grid(who, size, cell)
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name in names):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(names)}')
+    if state['peak'].dim() != 2:
+        raise ValueError(f'{who}: state peak must be [cameras, 2], got {tuple(state["peak"].shape)}')
+    cameras = state['peak'].shape[0]
+    S = state['id'].shape[1] if 'id' in names and state['id'].dim() == 2 else 1
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS} and S in 1 .. {native.TRACK_MAX_TRACKS}, got '
+                         f'{cameras} and {S}')
+    for name, kind in _HEAT_STATE:
+        if name not in names:
+            continue
+        t, want = state[name], ((cameras,), (cameras, S), (cameras, 2), (cameras, Gh, Gw))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    return cameras, S, Gw, Gh
+
+
+def heat_update(entries, state, *, K, size, cell=8, radius=1, half_life=0, max_age=30, anchor='feet', anchor_kpts=(),
+                score_thr=0.3, kpt_thr=0.):
+    """Footfall maps from frames of tracked poses, one launch per 32 frames (pave_heat_update; the rule is DESIGN
+    section 21).  entries: what `zone_events` takes, one (kpts, bboxes, keep, ids, camera, (sx, sy)) per frame, the
+    frames of one camera in time order; state: int32 device tensors id, last, cell [cameras, S], frame, dropped
+    [cameras], peak [cameras, 2] and dwell, visits [cameras, Gh, Gw], read and written; size (width, height) in
+    original-image pixels 1 .. 8192, cell 4 | 8 | 16 | 32 | 64 with at most 512 cells a side, radius 0 .. 3, half_life
+    0 .. 2^18; anchor and anchor_kpts as in `zone_events`.  Returns one dict(cell [N], dwell [N], visits [N]) of new
+    int32 tensors per entry.  Shapes, types and ranges raise ValueError before anything is asked of a device."""
+    who = 'heat_update'
+    entries = list(entries)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= native.TRACK_MAX_K:
+        raise ValueError(f'{who}: K must be an integer in 1 .. {native.TRACK_MAX_K}, got {K!r}')
+    cameras, S, Gw, Gh = _heat_state(who, state, [n for n, _ in _HEAT_STATE], size, cell)
+    for name, v, lo, hi in (('radius', radius, 0, native.HEAT_MAX_RADIUS),
+                            ('half_life', half_life, 0, native.HEAT_MAX_HALF_LIFE)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    if anchor not in ZONE_ANCHORS:
+        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
+    anchor_kpts = list(anchor_kpts)
+    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
+            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
+        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
+                         f'{anchor_kpts!r}')
+    checked = []
+    for i, entry in enumerate(entries):
+        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
+            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
+        kpts, bboxes, keep, ids, camera, scale = entry
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
+            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
+        if N > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+        try:
+            sx, sy = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
+        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
+        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    # the shapes are right: now where the tensors live
+    dev = state['peak'].device
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n, _ in _HEAT_STATE):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if any(t is not None and t.device != dev for t in c[:4]):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    z = dict(dtype=torch.int32, device=dev)
+    outs = [dict(cell=torch.empty((c[7],), **z), dwell=torch.empty((c[7],), **z), visits=torch.empty((c[7],), **z))
+            for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.HeatPlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
+            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+                _ptr(keep) or None, _ptr(ids) or None
+            out = outs[at + i]
+            plan.out_cell[i], plan.out_dwell[i], plan.out_visits[i] = (out[n].data_ptr() or None
+                                                                       for n in ('cell', 'dwell', 'visits'))
+            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+        (plan.slot_id, plan.slot_last, plan.slot_cell, plan.frame, plan.dropped, plan.peak, plan.dwell, plan.visits) = (
+            state[n].data_ptr() for n, _ in _HEAT_STATE)
+        for i, k in enumerate(anchor_kpts):
+            plan.anchor_kpt[i] = k
+        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
+        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
+        plan.width, plan.height, plan.cell, plan.radius = int(size[0]), int(size[1]), cell, radius
+        plan.half_life, plan.max_age = half_life, int(max_age)
+        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        _launch('pave_heat_update', who, dev, ctypes.byref(plan))
+    return outs
+
+
+def draw_heat(kind, items, state, palette, *, size, cell=8, source='dwell', full_scale=None, alpha_max=160, floor=1,
+              smooth=True):
+    """A footfall map blended into surfaces in place, one launch per 32 surfaces (pave_draw_heat_nv12 / _bgr; the rule
+    is DESIGN section 21).  kind 'nv12' | 'bgr' and a surface as in draw_zones.  items: one (surface, width, camera,
+    table) per surface.  state: the map's int32 device tensors dwell, visits [cameras, Gh, Gw] and peak [cameras, 2],
+    read only.  palette: a uint8 device tensor [tables, 256, 3], 1 .. 8 tables of the 256 colours by level, stored or
+    blended as they are.  size, cell: the map's; source 'dwell' | 'visits'; full_scale an integer 1 .. 2^31 - 1 or None
+    (the map's peak, read on the device); alpha_max 0 .. 256, floor 0 .. 255.  Shapes, types and ranges raise
+    ValueError before anything is asked of a device."""
+    who = 'draw_heat'
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
+    items = list(items)
+    if not items:
+        raise ValueError(f'{who}: no surface')
+    if any(not (isinstance(it, (tuple, list)) and len(it) == 4) for it in items):
+        raise ValueError(f'{who}: an item is (surface, width, camera, table)')
+    if source not in HEAT_SOURCES:
+        raise ValueError(f'{who}: source is one of {", ".join(HEAT_SOURCES)}, got {source!r}')
+    for name, v, lo, hi in (('alpha_max', alpha_max, 0, 256), ('floor', floor, 0, 255)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} is an integer in {lo} .. {hi}, got {v!r}')
+    if full_scale is not None and (isinstance(full_scale, bool) or not isinstance(full_scale, int)
+                                   or not 1 <= full_scale <= 2 ** 31 - 1):
+        raise ValueError(f'{who}: full_scale is None or an integer in 1 .. 2^31 - 1, got {full_scale!r}')
+    cameras, _, Gw, Gh = _heat_state(who, state, ('peak', 'dwell', 'visits'), size, cell)
+    if not (isinstance(palette, torch.Tensor) and palette.dtype == torch.uint8 and palette.dim() == 3
+            and 1 <= palette.shape[0] <= native.HEAT_MAX_TABLES and tuple(palette.shape[1:]) == (256, 3)
+            and palette.is_contiguous()):
+        raise ValueError(f'{who}: palette is a contiguous uint8 [1 .. {native.HEAT_MAX_TABLES}, 256, 3] tensor')
+    tables = palette.shape[0]
+    geometry = []
+    for i, (surf, width, camera, table) in enumerate(items):
+        if not (isinstance(surf, torch.Tensor) and surf.dtype == torch.uint8):
+            raise ValueError(f'{who}: surface {i} must be a uint8 tensor')
+        if kind == 'nv12':
+            if surf.dim() != 2:
+                raise ValueError(f'{who}: surface {i} must be [H * 3 // 2, pitch], got {tuple(surf.shape)}')
+            if isinstance(width, bool) or not isinstance(width, numbers.Integral):
+                raise ValueError(f'{who}: the width of surface {i} must be an integer, got {width!r}')
+            rows, pitch = surf.shape
+            H, W, row_bytes = rows * 2 // 3, int(width), int(width)
+            if rows % 3 != 0 or H % 2 != 0 or H <= 0:
+                raise ValueError(f'{who}: surface {i}: {rows} rows are not the 3/2 of an even height')
+            if W <= 0 or W % 2 != 0:
+                raise ValueError(f'{who}: surface {i}: width {W} must be even and positive')
+        else:
+            if surf.dim() != 3 or surf.shape[2] != 3 or surf.shape[0] < 1 or surf.shape[1] < 1:
+                raise ValueError(f'{who}: surface {i} must be [H, W, 3], got {tuple(surf.shape)}')
+            H, W = surf.shape[:2]
+            row_bytes = 3 * W
+            pitch = row_bytes if surf.is_contiguous() else surf.stride(0)     # (rows of a wider buffer)
+            if not surf.is_contiguous() and (surf.stride(2) != 1 or surf.stride(1) != 3):
+                raise ValueError(f'{who}: surface {i} must be contiguous, or contiguous rows of a wider buffer')
+        if row_bytes > pitch:
+            raise ValueError(f'{who}: surface {i}: width {W} exceeds the pitch {pitch}')
+        if W > native.DRAW_MAX_SIZE or H > native.DRAW_MAX_SIZE:
+            raise ValueError(f'{who}: surface {i}: {W} x {H} exceeds {native.DRAW_MAX_SIZE} x {native.DRAW_MAX_SIZE}')
+        if kind == 'nv12' and not surf.is_contiguous():
+            raise ValueError(f'{who}: surface {i} must be contiguous')
+        if isinstance(camera, bool) or not isinstance(camera, numbers.Integral) or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of surface {i} must be an integer in [0, {cameras}), got {camera!r}')
+        if isinstance(table, bool) or not isinstance(table, numbers.Integral) or not 0 <= table < tables:
+            raise ValueError(f'{who}: surface {i} names palette table {table} of {tables}')
+        geometry.append((int(pitch), int(W), int(H), int(camera), int(table)))
+    # the shapes are right: now where the tensors live
+    dev = state['peak'].device
+    if dev.type != 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n in ('dwell', 'visits')) or palette.device != dev:
+        raise ValueError(f'{who}: the state tensors and the palette must be on one device ({dev})')
+    for i, it in enumerate(items):
+        if it[0].device != dev:
+            raise ValueError(f"{who}: surface {i} is on {it[0].device}, the map on {dev}")
+    entry = 'pave_draw_heat_nv12' if kind == 'nv12' else 'pave_draw_heat_bgr'
+    for at in range(0, len(items), native.DRAW_MAX_SURFACES):
+        plan = native.HeatDrawPlan()
+        part = items[at:at + native.DRAW_MAX_SURFACES]
+        for i, it in enumerate(part):
+            plan.dst[i] = it[0].data_ptr()
+            plan.pitch[i], plan.width[i], plan.height[i], plan.camera[i], plan.table[i] = geometry[at + i]
+        plan.map, plan.peak, plan.palette = state[source].data_ptr(), state['peak'].data_ptr(), palette.data_ptr()
+        plan.n, plan.cameras, plan.tables = len(part), cameras, tables
+        plan.map_width, plan.map_height, plan.cell = int(size[0]), int(size[1]), cell
+        plan.source, plan.full_scale = HEAT_SOURCES.index(source), 0 if full_scale is None else full_scale
+        plan.alpha_max, plan.floor, plan.smooth = alpha_max, floor, 1 if smooth else 0
+        _launch(entry, who, dev, ctypes.byref(plan))
+
+
 _REID_STATE = (('person', 1), ('track', 1), ('last', 1), ('hits', 2), ('hist', 3), ('frame', 0), ('next', 0),
                ('dropped', 0))   # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 2, 256]
 
