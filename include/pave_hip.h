@@ -1427,8 +1427,9 @@ int pave_swin_window_attn_f32(const float* qkv, const float* bias_t, const float
  */
 int pave_merge_softmax_partials_f32(const float* parts, float* out, int G, int U, int C, int H, void* stream);
 
-/* x[n] fp32 -> planes[nplanes][n] bf16: truncation terms, the last rounded to nearest even
- * (nplanes = 3: x = p0 + p1 + p2 exactly). */
+/* x[n] fp32 -> planes[nplanes][n] bf16.  nplanes = 3: every term rounded to nearest even, x = p0 + p1 + p2
+ * exactly (the terms' signs are independent of x's: with the activations' truncation split on the other side the
+ * products a kernel leaves out average to zero);  2: a truncation term, then the remainder rounded;  1: x rounded. */
 int pave_split_bf16x3_f32(const float* x, void* planes, long long n, int nplanes, void* stream);
 
 /*

@@ -13,7 +13,8 @@
 // integer operands whose partial sums stay below 2^24 and whose bracket is identically zero
 // every form of this file and of pave_gemm_dma.hip -- whatever its summation order -- must give
 // the bits of the int64 result) at 2.5 PF / 6 = 417 TFLOP/s peak, 2.7x the fp32
-// MFMA rate.  Weights are split once on the host side (pave_split_bf16x3_f32); activations are
+// MFMA rate.  Weights are split once on the host side (pave_split_bf16x3_f32: by ROUNDING each term, just as
+// exact -- see split_bf16x3_kernel for why the two operands must not both be truncated); activations are
 // split while they are staged into LDS, so HBM traffic is that of an fp32 GEMM.
 //
 //   out[M, N] = act(A'[M, K] * W[N, K]^T + bias[N] + residual[M, N]),
@@ -527,17 +528,33 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                                            a_bias, g, os, ln);
 }
 
-// fp32 [n] -> nplanes bf16 planes [nplanes][n]: truncation terms, the last one rounded to
-// nearest even (nplanes = 3: x = p0 + p1 + p2 exactly)
+// v rounded to nearest even at bf16, as fp32 bits (a value that would round to infinity, and inf / NaN: cut)
+__device__ __forceinline__ unsigned rne16(float v) {
+  const unsigned r = (pack_rne<false>(v, 0.f) & 0xffffu) << 16;
+  return (r & 0x7f800000u) == 0x7f800000u ? hi16(v) : r;
+}
+
+// fp32 [n] -> nplanes bf16 planes [nplanes][n]  (the WEIGHT operand: split once, off the hot path).
+// nplanes = 3: x = p0 + p1 + p2 exactly, every term ROUNDED to nearest even (the residual of an 8-bit rounding of
+// a 24-bit significand has 16 bits, that of the second rounding at most 8: the last term is exact).  Why not the
+// truncation split the kernels apply to the activation rows: truncated terms all carry the value's own sign, and
+// with BOTH operands split that way the three products the kernels leave out, a1 b2 + a2 b1 + a2 b2, have the sign
+// of a b -- every product of every GEMM comes out smaller in magnitude by about 2^-24 of itself.  Inside one GEMM
+// that is below fp32's own rounding, but it is the same sign in every layer: behind the ~80 convolutions of an
+// HRNet-w48 the stage outputs sat 9.3 x the fp32 floor off the fp64 result (tests/test_backbone_gpu.py).  With the
+// weight's terms rounded their signs are independent of the weight's, and the left-out products average to zero
+// (the same outputs: 4.7 x the floor, ResNet-50's 3.1 -> 2.6).
+// nplanes = 2: a truncation term, then the remainder rounded;  1: the value rounded (bf16 or fp16).
 __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float* __restrict__ x,
                                                            uint16_t* __restrict__ planes,
                                                            const long long n, const int nplanes,
                                                            const int f16) {
+  const bool rounded = nplanes == 3;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n;
        i += (long long)gridDim.x * 256) {
     float v = x[i];
     for (int t = 0; t < nplanes - 1; ++t) {
-      const unsigned h = hi16(v);
+      const unsigned h = rounded ? rne16(v) : hi16(v);
       planes[t * n + i] = (uint16_t)(h >> 16);
       v -= __uint_as_float(h);
     }

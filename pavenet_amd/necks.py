@@ -84,8 +84,9 @@ class ChannelMapper(BaseModule):
             if wsplit is None:
                 return None
             xc = x.contiguous(memory_format=torch.channels_last)
+            # (cout: the planes are zero-padded to Cout % 64 == 0; the kernel stores the real channels)
             return ops.conv3x3_split(xc, wsplit, None, stride=conv.stride[0], relu=False,
-                                     fp16=get_gemm_mode() == 'fp16')
+                                     fp16=get_gemm_mode() == 'fp16', cout=conv.out_channels)
         return None
 
     def _forward_flat(self, inputs):

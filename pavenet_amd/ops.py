@@ -1762,8 +1762,9 @@ def bias_act_rows_(x, bias=None, res=None, relu=True):
     """In place: x[r, c] = act(x[r, c] + bias[c] + res[r, c]) over the last (channel) dim.
     `x` must be dense with channels innermost (token matrix, or an NHWC / channels_last map)."""
     _require(x.is_cuda and x.dtype == torch.float32, 'bias_act_rows_: fp32 device tensor')
+    # (a 1x1 map [N, C, 1, 1] is dense in both layouts: its rows are the N pixels' channels either way)
     nhwc = x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) \
-        and not x.is_contiguous()
+        and (not x.is_contiguous() or (x.shape[2] == 1 and x.shape[3] == 1))
     C = bias.numel() if bias is not None else (x.shape[1] if nhwc else x.shape[-1])
     if nhwc:
         _require(x.shape[1] == C, 'bias_act_rows_: channel mismatch')
@@ -1981,9 +1982,9 @@ def bias_relu_maxpool_nhwc(x, bias):
 
 
 def split_bf16x3(x, planes=3):
-    """fp32 tensor -> int16 tensor [planes, *x.shape] of bf16 bit patterns: truncation terms, the
-    last rounded to nearest (planes = 3: x == p0 + p1 + p2 exactly).  planes = PLANES_FP16: one
-    plane of fp16 bit patterns."""
+    """fp32 tensor -> int16 tensor [planes, *x.shape] of bf16 bit patterns.  planes = 3: rounded terms,
+    x == p0 + p1 + p2 exactly (the weight operand: include/pave_hip.h says why rounded);  2: a truncation
+    term and the rounded remainder;  1: x rounded.  planes = PLANES_FP16: one plane of fp16 bit patterns."""
     _dev(x, 'x', torch.float32)
     _require(planes in (1, 2, 3, PLANES_FP16), 'split_bf16x3: planes must be 1, 2, 3 or PLANES_FP16')
     n_out = 1 if planes == PLANES_FP16 else planes

@@ -2,12 +2,14 @@
 every summation order gives the same fp32 bits, the int64-exact expected values, and an fp32 emulation of the
 six-product accumulation (numpy / torch on the CPU only; tests/test_int_gemm_ref_cpu.py, tests/test_gemm_exact_gpu.py).
 
-Why a zero tolerance holds.  The truncation split of an fp32 value (csrc/pave_gemm_split.hip) gives planes of the
-value's own sign, so sum_i |a_i| == |a|; the planes of an integer are integers; and a product of two bf16 (or fp16)
-values is exact in the matrix core's fp32 datapath.  Every partial sum of any subset of the plane products, in any
-order, is then an integer of magnitude <= sum_k |a_ik| |w_jk| (+ |bias| + |residual|).  Where that bound is <= 2^24
-no addition rounds, whatever the kernel's tile order, K-split or split-K plan: the output IS the integer result,
-provided the products the kernel does not compute (a1 b2 + a2 b1 + a2 b2 with three planes) are zero.
+Why a zero tolerance holds.  The kernels split an activation by truncation (csrc/pave_gemm_split.hip): planes of
+the value's own sign, so sum_i |a_i| == |a|.  The three weight planes are ROUNDED terms (split_bf16x3_kernel: with both
+operands truncated the products a kernel leaves out would all have the sign of a b), so they may differ in sign and
+sum_j |w_j| can exceed |w| by up to 2^-7 |w|.  The planes of an integer are integers either way, and a product of two
+bf16 (or fp16) values is exact in the matrix core's fp32 datapath.  Every partial sum of any subset of the plane
+products, in any order, is then an integer of magnitude <= sum_k |a_ik| sum_j |w_j|_jk (+ |bias| + |residual|).  Where
+that bound is <= 2^24 no addition rounds, whatever the kernel's tile order, K-split or split-K plan: the output IS the
+integer result, provided the products the kernel does not compute (a1 b2 + a2 b1 + a2 b2 with three planes) are zero.
 """
 import numpy as np
 import torch
@@ -27,14 +29,35 @@ ALL_PRODUCTS = ((0, 0), (0, 1), (1, 0), (0, 2), (1, 1), (2, 0))      # what a 3-
 COMPUTED = {3: ALL_PRODUCTS, 2: ((0, 0), (0, 1), (1, 0)), 1: ((0, 0),)}
 A3_NNZ, X2_NNZ = 120, 60      # non-zeros per sparse row (the issue's caps are 128 and 64; the slack pays for the
 #                               a_bias prologue, which raises |a'| by up to 15)
+W3_NNZ = 40                   # W3's sparse a: its weights have 18 bits (a rounded split puts 17 into two planes), and
+#                               the four columns that are always non-zero weigh more in the 3x3 / 7x7 forms' rows
 
 
 def _hi16(x):
     return (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & np.uint32(0xffff0000)).view(np.float32)
 
 
+def _rne16(x):
+    """x rounded to nearest even at bf16 (finite values below the largest bf16)."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return ((u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xffff0000)).view(np.float32)
+
+
+def split3_w(x):
+    """The split of a WEIGHT (csrc/pave_gemm_split.hip, split_bf16x3_kernel with three planes) on the host: two
+    rounded terms and the exact remainder, x == p0 + p1 + p2, each a bf16 value."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    p0 = _rne16(x)
+    r1 = x - p0
+    p1 = _rne16(r1)
+    p2 = r1 - p1
+    assert np.array_equal(_hi16(p2), p2)
+    return p0, p1, p2
+
+
 def split3(x):
-    """The truncation split of csrc/pave_gemm_split.hip on the host: x == p0 + p1 + p2, each a bf16 value."""
+    """The truncation split of an ACTIVATION (csrc/pave_gemm_split.hip, and of the weights of the 2-plane mode) on
+    the host: x == p0 + p1 + p2, each a bf16 value."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     p0 = _hi16(x)
     r1 = x - p0
@@ -76,7 +99,7 @@ def operands(family, M, K, N, seed=0):
     elif family == 'A3':
         a, w = _wide(rng, (M, K), 16), _sparse_signs(rng, N, K, A3_NNZ)
     elif family == 'W3':
-        a, w = _sparse_signs(rng, M, K, A3_NNZ), _wide(rng, (N, K), 16)
+        a, w = _sparse_signs(rng, M, K, W3_NNZ), _wide(rng, (N, K), 17)
     elif family == 'X2':
         a = _wide(rng, (M, K), 8)
         w = _sparse_signs(rng, N, K, X2_NNZ) * np.abs(_wide(rng, (N, K), 8))
@@ -123,7 +146,9 @@ def check_case(a, w, bias=None, residual=None, a_bias=None, planes=3, family=Non
     ap = prologue(a, a_bias)
     for name, t in (('a', ap), ('w', w), ('bias', bias), ('residual', residual)):
         assert t is None or np.array_equal(t, np.rint(t)), f'{name}: integers only'
-    bound = np.abs(ap).astype(np.float64) @ np.abs(w).astype(np.float64).T
+    # (three planes: the rounded weight terms may differ in sign -- the partial sums are bounded by sum_j |w_j|)
+    wmag = np.abs(w) if planes != 3 else sum(np.abs(p) for p in split3_w(w))
+    bound = np.abs(ap).astype(np.float64) @ wmag.astype(np.float64).T
     bound = bound + (0 if bias is None else np.abs(bias)[None, :])
     bound = bound.max() + (0 if residual is None else np.abs(residual).max())
     assert bound <= EXACT, f'sum |a||w| + |bias| + |res| = {bound} > 2^24'
@@ -131,7 +156,7 @@ def check_case(a, w, bias=None, residual=None, a_bias=None, planes=3, family=Non
         for name, t in (('a', ap), ('w', w)):
             assert np.array_equal(t.astype(np.float16).astype(np.float32), t), f'{name}: not an fp16 value'
         return bound
-    sa, sw = split3(ap), split3(w)
+    sa, sw = split3(ap), (split3_w if planes == 3 else split3)(w)
     assert np.array_equal(sa[0] + sa[1] + sa[2], ap) and np.array_equal(sw[0] + sw[1] + sw[2], w)
     live_a = [bool(p.any()) for p in sa]
     live_w = [bool(p.any()) for p in sw]
@@ -177,10 +202,11 @@ def layernorm64(x, gamma, beta, eps):
     return (x - mu) / np.sqrt(var + eps) * gamma[None, :].astype(np.float64) + beta[None, :].astype(np.float64)
 
 
-def emulate(a, w, products=ALL_PRODUCTS, k_order=None, planes_of=split3):
+def emulate(a, w, products=ALL_PRODUCTS, k_order=None, planes_of=None):
     """fp32 accumulation of the plane products a_i[:, k] b_j[:, k] over k in `k_order` (default: natural), the
-    products of one k in the order given: what a kernel that sums in this order computes."""
-    sa, sw = planes_of(a), planes_of(w)
+    products of one k in the order given: what a kernel that sums in this order computes.  planes_of: the split of
+    both operands (default: the 3-plane kernels' -- activations truncated, weights rounded)."""
+    sa, sw = (split3(a), split3_w(w)) if planes_of is None else (planes_of(a), planes_of(w))
     acc = np.zeros((a.shape[0], w.shape[0]), dtype=np.float32)
     for k in (range(a.shape[1]) if k_order is None else k_order):
         for i, j in products:

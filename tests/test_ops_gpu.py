@@ -509,6 +509,25 @@ def test_bias_act_rows_vs_torch():
     np.testing.assert_allclose(out.cpu().numpy(), (t + bias.repeat(2)).numpy(), rtol=0, atol=0)
 
 
+@pytest.mark.parametrize('n', [1, 3])
+def test_bias_act_rows_on_a_1x1_map(n):
+    """A 1x1 map [N, C, 1, 1] (ResNet layer4 of a 32 x 32 frame, HRNet's coarsest branch) is dense in the NCHW and
+    the channels_last sense at once; it was taken for a token matrix whose last dim (1) is not C and refused with
+    'channels must be innermost'.  Its rows are the N pixels' channels either way."""
+    from pavenet_amd.ops import bias_act_rows_
+    g = torch.Generator().manual_seed(6)
+    x = torch.randn(n, 64, 1, 1, generator=g)
+    res = torch.randn(n, 64, 1, 1, generator=g)
+    bias = torch.randn(64, generator=g)
+    exp = torch.relu(x + bias.view(1, -1, 1, 1) + res)
+    xd = x.cuda().contiguous(memory_format=torch.channels_last)
+    out = bias_act_rows_(xd, bias.cuda(), res.cuda(), relu=True)
+    assert out.data_ptr() == xd.data_ptr() and out.shape == x.shape
+    np.testing.assert_allclose(out.cpu().numpy(), exp.numpy(), rtol=0, atol=0)
+    out = bias_act_rows_(x.cuda(), bias.cuda(), None, relu=False)
+    np.testing.assert_allclose(out.cpu().numpy(), (x + bias.view(1, -1, 1, 1)).numpy(), rtol=0, atol=0)
+
+
 @pytest.mark.parametrize('sigma', [0.7, 3.0, 12.0])
 @pytest.mark.parametrize('gr', [False, True])
 @pytest.mark.parametrize('variant', [0, 1])
@@ -2382,6 +2401,28 @@ def test_neck_1x1_level_with_96_channels_runs_the_split_gemm():
         bricks.set_gemm_mode(old)
     assert y is not None, 'the K = 96 level fell back to the library'
     exp = torch.nn.functional.conv2d(x.double(), conv.weight.double())
+    np.testing.assert_allclose(y.detach().cpu().numpy(), exp.detach().cpu().numpy(), rtol=1e-5, atol=1e-5)
+
+
+def test_neck_3x3_level_with_96_output_channels_keeps_its_width():
+    """ChannelMapper's extra level (3x3, stride 2, no bias) with out_channels = 96: the split planes are zero-padded
+    to 128 output channels, and the launch must be told the real width -- the level came back 128 channels wide
+    (32 zero maps behind the real ones) and `_forward_flat` could not reshape it.  Against conv2d in fp64."""
+    from pavenet_amd import bricks
+    from pavenet_amd.necks import ChannelMapper
+    g = torch.Generator().manual_seed(97)
+    conv = torch.nn.Conv2d(256, 96, 3, stride=2, padding=1, bias=False).cuda()
+    x = torch.randn(2, 256, 9, 13, generator=g).cuda()
+    old = bricks.get_gemm_mode()
+    try:
+        bricks.set_gemm_mode('bf16x3')
+        with torch.no_grad():
+            y = ChannelMapper._conv_split(conv, x)
+    finally:
+        bricks.set_gemm_mode(old)
+    assert y is not None, 'the 3x3 level fell back to the library'
+    assert tuple(y.shape) == (2, 96, 5, 7)
+    exp = torch.nn.functional.conv2d(x.double(), conv.weight.double(), None, 2, 1)
     np.testing.assert_allclose(y.detach().cpu().numpy(), exp.detach().cpu().numpy(), rtol=1e-5, atol=1e-5)
 
 
