@@ -1079,6 +1079,108 @@ int pave_draw_heat_nv12(const pave_heat_draw_plan* plan, void* stream);
 int pave_draw_heat_bgr(const pave_heat_draw_plan* plan, void* stream);
 
 /*
+ * Track trails: the recent path of every tracked person, kept per camera in a ring of points per slot, and the paths
+ * as tapered lines in the picture (pavenet_amd/csrc/pave_trails.hip; the rules are DESIGN section 22, integer-exact).
+ * The plans are copied into the kernels' arguments.
+ *
+ * pave_trail_update: one launch for `entries` frames of any of `cameras` cameras; one block per camera of the launch
+ * takes that camera's entries in plan order, as pave_zone_events does: entries of one camera are in time order.
+ *   kpts[i], bboxes[i], keep[i], ids[i], n[i], camera[i], scale[i], anchor, anchor_kpt, n_anchor, S, K, max_age,
+ *   score_thr, kpt_thr   as in pave_zone_plan: the same poses take part and stand on the same 1/8-pixel anchor
+ *   out_count[i], out_span[i], out_dist[i], out_path[i]   DEVICE [n[i]] int32, out: the committed points of the pose's
+ *                    slot, the frames since the oldest of them, floor |pos - oldest| and the length along the points
+ *                    to pos (1/8 pixel); 0 for a pose that takes no part (all four may be NULL where n[i] == 0)
+ *   the state, DEVICE int32, read and written: slot_id, slot_last, slot_head, slot_count [cameras, S] (id 0: a free
+ *                    slot, its other fields are never read), slot_pos [cameras, S, 2], slot_box [cameras, S, 4] (x0,
+ *                    y0, x1, y1 over the committed points and pos), pts [cameras, S, L, 2], when [cameras, S, L] (the
+ *                    ring: point `head` is the newest, `count` of them are committed); frame, dropped [cameras]
+ *   L                1 .. PAVE_TRAIL_MAX_POINTS: points of a ring
+ *   stride           1 .. 255: frames between two commits at the least
+ *   min_step         0 .. 65535: 1/8 pixels (Chebyshev) between two committed points at the least
+ * Refused with PAVE_E_ARG before any device call: whatever pave_zone_events refuses in the fields of the same name, a
+ * null state or output tensor, L outside 1 .. 64, stride outside 1 .. 255, min_step outside 0 .. 65535.
+ * slot_head is reduced to (unsigned)head % L and slot_count clamped to 1 .. L wherever they index the ring, and a
+ * slot index is a loop counter: a plan that passes cannot address memory outside its tensors, whatever the poses and
+ * the state hold.
+ *
+ * pave_draw_trails_nv12 / _bgr: one launch for n separately allocated surfaces, in place; the state is only read.
+ *   dst, pitch, width, height, table, camera: as in pave_zone_draw_plan
+ *   slot_id .. frame: the tensors of pave_trail_plan, for every camera;  S, L: their sizes
+ *   palette    the bytes stored, per table: (Y, U, V) for _nv12, (B, G, R) for _bgr; a slot takes row (id - 1) % 32
+ *   thickness, thickness_tail   1 .. 32 pixels at the newest and the oldest end, thickness_tail <= thickness
+ *   head_radius  0 .. 32 pixels: a disc at pos (0: none)
+ *   tail_frames  0 (every segment) or 1 .. 2^30: a segment whose older point was committed more than this many
+ *                frames ago is not drawn
+ *   linger     -1 (every live slot) or 0 .. 2^30: only slots seen within the last `linger` frames
+ * A point in quarter pixels is Q = clamp(p >> 1, 0, 32767).  With n = count and p_0 .. p_{n-1} the committed points,
+ * oldest first, p_n = pos: capsule j = 0 .. n - 1 from Q(p_j) to Q(p_{j+1}) of radius 2 thickness_tail + floor(2
+ * (thickness - thickness_tail)(j + 1) / n) quarter pixels, and (head_radius > 0) the disc j = n at Q(pos) of radius 4
+ * head_radius; covered as in pave_draw_plan.  A pixel takes the colour of the covering primitive with the largest
+ * (id, j); an NV12 chroma sample the largest over its 2 x 2 luma pixels.  A byte no primitive covers and padding are
+ * never written.
+ * Refused with PAVE_E_ARG before any device call: a null plan, surface or state tensor, n outside 1 .. 32, width or
+ * height outside 1 .. 8192, odd NV12 sizes, a pitch below a row's bytes, a table index >= 4, cameras outside 1 ..
+ * 4096, a camera outside [0, cameras), S outside 1 .. 128, L outside 1 .. 64, thickness or thickness_tail outside 1 ..
+ * 32 or thickness_tail > thickness, head_radius outside 0 .. 32, tail_frames outside 0 .. 2^30, linger outside -1 ..
+ * 2^30.  head and count are reduced as in the update before they index the ring.
+ */
+#define PAVE_TRAIL_MAX_POINTS 64
+#define PAVE_TRAIL_MAX_STRIDE 255
+#define PAVE_TRAIL_MAX_STEP 65535
+#define PAVE_TRAIL_MAX_THICKNESS 32
+#define PAVE_TRAIL_MAX_RADIUS 32
+#define PAVE_TRAIL_MAX_FRAMES 1073741824
+typedef struct pave_trail_plan {
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_count[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_span[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_dist[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_path[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int32_t* slot_id;
+  int32_t* slot_last;
+  int32_t* slot_pos;
+  int32_t* slot_head;
+  int32_t* slot_count;
+  int32_t* slot_box;
+  int32_t* pts;
+  int32_t* when;
+  int32_t* frame;
+  int32_t* dropped;
+  int anchor_kpt[PAVE_ZONE_MAX_ANCHOR_KPTS];
+  int entries, cameras, S, K, L, anchor, n_anchor, stride, min_step, max_age;
+  float score_thr, kpt_thr;
+} pave_trail_plan;
+int pave_trail_update(const pave_trail_plan* plan, void* stream);
+
+typedef struct pave_trail_draw_plan {
+  void*          dst[PAVE_DRAW_MAX_SURFACES];
+  int            pitch[PAVE_DRAW_MAX_SURFACES];
+  int            width[PAVE_DRAW_MAX_SURFACES];
+  int            height[PAVE_DRAW_MAX_SURFACES];
+  int            camera[PAVE_DRAW_MAX_SURFACES];
+  uint8_t        table[PAVE_DRAW_MAX_SURFACES];
+  const int32_t* slot_id;
+  const int32_t* slot_last;
+  const int32_t* slot_pos;
+  const int32_t* slot_head;
+  const int32_t* slot_count;
+  const int32_t* slot_box;
+  const int32_t* pts;
+  const int32_t* when;
+  const int32_t* frame;
+  uint8_t        palette[PAVE_DRAW_MAX_TABLES][PAVE_DRAW_PALETTE][3];
+  int n, cameras, S, L, thickness, thickness_tail, head_radius, tail_frames, linger;
+} pave_trail_draw_plan;
+int pave_draw_trails_nv12(const pave_trail_draw_plan* plan, void* stream);
+int pave_draw_trails_bgr(const pave_trail_draw_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

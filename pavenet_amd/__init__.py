@@ -56,6 +56,9 @@ def __getattr__(name):
     if name in ('FootfallMap', 'HeatStyle', 'draw_heat_nv12', 'draw_heat_bgr'):
         from . import heatmap
         return getattr(heatmap, name)
+    if name in ('TrackTrails', 'TrailStyle', 'draw_trails_nv12', 'draw_trails_bgr'):
+        from . import trails
+        return getattr(trails, name)
     if name == 'PersonReID':
         from . import reid
         return reid.PersonReID

@@ -326,6 +326,42 @@ class HeatDrawPlan(ctypes.Structure):
                 ('smooth', ctypes.c_int)]
 
 
+TRAIL_MAX_POINTS, TRAIL_MAX_STRIDE, TRAIL_MAX_STEP, TRAIL_MAX_THICKNESS, TRAIL_MAX_RADIUS, TRAIL_MAX_FRAMES = (
+    DEFINES['PAVE_TRAIL_MAX_' + n] for n in ('POINTS', 'STRIDE', 'STEP', 'THICKNESS', 'RADIUS', 'FRAMES'))
+
+
+class TrailPlan(ctypes.Structure):
+    """`pave_trail_plan` of include/pave_hip.h (the by-value argument of pave_trail_update)."""
+    _fields_ = [('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_count', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_span', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_dist', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_path', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('n', ctypes.c_int * TRACK_MAX_FRAMES), ('camera', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES), ('slot_id', ctypes.c_void_p),
+                ('slot_last', ctypes.c_void_p), ('slot_pos', ctypes.c_void_p), ('slot_head', ctypes.c_void_p),
+                ('slot_count', ctypes.c_void_p), ('slot_box', ctypes.c_void_p), ('pts', ctypes.c_void_p),
+                ('when', ctypes.c_void_p), ('frame', ctypes.c_void_p), ('dropped', ctypes.c_void_p),
+                ('anchor_kpt', ctypes.c_int * ZONE_MAX_ANCHOR_KPTS), ('entries', ctypes.c_int),
+                ('cameras', ctypes.c_int), ('S', ctypes.c_int), ('K', ctypes.c_int), ('L', ctypes.c_int),
+                ('anchor', ctypes.c_int), ('n_anchor', ctypes.c_int), ('stride', ctypes.c_int),
+                ('min_step', ctypes.c_int), ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float),
+                ('kpt_thr', ctypes.c_float)]
+
+
+class TrailDrawPlan(ctypes.Structure):
+    """`pave_trail_draw_plan` of include/pave_hip.h (the by-value argument of pave_draw_trails_nv12 / _bgr)."""
+    _fields_ = [('dst', ctypes.c_void_p * DRAW_MAX_SURFACES), ('pitch', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('width', ctypes.c_int * DRAW_MAX_SURFACES), ('height', ctypes.c_int * DRAW_MAX_SURFACES),
+                ('camera', ctypes.c_int * DRAW_MAX_SURFACES), ('table', ctypes.c_uint8 * DRAW_MAX_SURFACES),
+                ('slot_id', ctypes.c_void_p), ('slot_last', ctypes.c_void_p), ('slot_pos', ctypes.c_void_p),
+                ('slot_head', ctypes.c_void_p), ('slot_count', ctypes.c_void_p), ('slot_box', ctypes.c_void_p),
+                ('pts', ctypes.c_void_p), ('when', ctypes.c_void_p), ('frame', ctypes.c_void_p),
+                ('palette', ((ctypes.c_uint8 * 3) * DRAW_PALETTE) * DRAW_MAX_TABLES), ('n', ctypes.c_int),
+                ('cameras', ctypes.c_int), ('S', ctypes.c_int), ('L', ctypes.c_int), ('thickness', ctypes.c_int),
+                ('thickness_tail', ctypes.c_int), ('head_radius', ctypes.c_int), ('tail_frames', ctypes.c_int),
+                ('linger', ctypes.c_int)]
+
+
 _lib = None
 
 

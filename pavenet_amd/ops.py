@@ -1397,33 +1397,9 @@ def _heat_state(who, state, names, size, cell):
     return cameras, S, Gw, Gh
 
 
-def heat_update(entries, state, *, K, size, cell=8, radius=1, half_life=0, max_age=30, anchor='feet', anchor_kpts=(),
-                score_thr=0.3, kpt_thr=0.):
-    """Footfall maps from frames of tracked poses, one launch per 32 frames (pave_heat_update; the rule is DESIGN
-    section 21).  entries: what `zone_events` takes, one (kpts, bboxes, keep, ids, camera, (sx, sy)) per frame, the
-    frames of one camera in time order; state: int32 device tensors id, last, cell [cameras, S], frame, dropped
-    [cameras], peak [cameras, 2] and dwell, visits [cameras, Gh, Gw], read and written; size (width, height) in
-    original-image pixels 1 .. 8192, cell 4 | 8 | 16 | 32 | 64 with at most 512 cells a side, radius 0 .. 3, half_life
-    0 .. 2^18; anchor and anchor_kpts as in `zone_events`.  Returns one dict(cell [N], dwell [N], visits [N]) of new
-    int32 tensors per entry.  Shapes, types and ranges raise ValueError before anything is asked of a device."""
-    who = 'heat_update'
-    entries = list(entries)
-    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= native.TRACK_MAX_K:
-        raise ValueError(f'{who}: K must be an integer in 1 .. {native.TRACK_MAX_K}, got {K!r}')
-    cameras, S, Gw, Gh = _heat_state(who, state, [n for n, _ in _HEAT_STATE], size, cell)
-    for name, v, lo, hi in (('radius', radius, 0, native.HEAT_MAX_RADIUS),
-                            ('half_life', half_life, 0, native.HEAT_MAX_HALF_LIFE)):
-        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-            raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
-        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
-    if anchor not in ZONE_ANCHORS:
-        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
-    anchor_kpts = list(anchor_kpts)
-    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
-            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
-        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
-                         f'{anchor_kpts!r}')
+def _tracked_entries(who, entries, K, cameras):
+    """The (kpts, bboxes, keep, ids, camera, sx, sy, N) of every (kpts, bboxes, keep, ids, camera, (sx, sy)) entry of
+    an update that follows track ids, or the ValueError."""
     checked = []
     for i, entry in enumerate(entries):
         if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
@@ -1453,6 +1429,37 @@ def heat_update(entries, state, *, K, size, cell=8, radius=1, half_life=0, max_a
         if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
             raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
         checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    return checked
+
+
+def heat_update(entries, state, *, K, size, cell=8, radius=1, half_life=0, max_age=30, anchor='feet', anchor_kpts=(),
+                score_thr=0.3, kpt_thr=0.):
+    """Footfall maps from frames of tracked poses, one launch per 32 frames (pave_heat_update; the rule is DESIGN
+    section 21).  entries: what `zone_events` takes, one (kpts, bboxes, keep, ids, camera, (sx, sy)) per frame, the
+    frames of one camera in time order; state: int32 device tensors id, last, cell [cameras, S], frame, dropped
+    [cameras], peak [cameras, 2] and dwell, visits [cameras, Gh, Gw], read and written; size (width, height) in
+    original-image pixels 1 .. 8192, cell 4 | 8 | 16 | 32 | 64 with at most 512 cells a side, radius 0 .. 3, half_life
+    0 .. 2^18; anchor and anchor_kpts as in `zone_events`.  Returns one dict(cell [N], dwell [N], visits [N]) of new
+    int32 tensors per entry.  Shapes, types and ranges raise ValueError before anything is asked of a device."""
+    who = 'heat_update'
+    entries = list(entries)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= native.TRACK_MAX_K:
+        raise ValueError(f'{who}: K must be an integer in 1 .. {native.TRACK_MAX_K}, got {K!r}')
+    cameras, S, Gw, Gh = _heat_state(who, state, [n for n, _ in _HEAT_STATE], size, cell)
+    for name, v, lo, hi in (('radius', radius, 0, native.HEAT_MAX_RADIUS),
+                            ('half_life', half_life, 0, native.HEAT_MAX_HALF_LIFE)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    if anchor not in ZONE_ANCHORS:
+        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
+    anchor_kpts = list(anchor_kpts)
+    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
+            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
+        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
+                         f'{anchor_kpts!r}')
+    checked = _tracked_entries(who, entries, K, cameras)
     # the shapes are right: now where the tensors live
     dev = state['peak'].device
     if not dev.type == 'cuda':
@@ -1488,37 +1495,9 @@ def heat_update(entries, state, *, K, size, cell=8, radius=1, half_life=0, max_a
     return outs
 
 
-def draw_heat(kind, items, state, palette, *, size, cell=8, source='dwell', full_scale=None, alpha_max=160, floor=1,
-              smooth=True):
-    """A footfall map blended into surfaces in place, one launch per 32 surfaces (pave_draw_heat_nv12 / _bgr; the rule
-    is DESIGN section 21).  kind 'nv12' | 'bgr' and a surface as in draw_zones.  items: one (surface, width, camera,
-    table) per surface.  state: the map's int32 device tensors dwell, visits [cameras, Gh, Gw] and peak [cameras, 2],
-    read only.  palette: a uint8 device tensor [tables, 256, 3], 1 .. 8 tables of the 256 colours by level, stored or
-    blended as they are.  size, cell: the map's; source 'dwell' | 'visits'; full_scale an integer 1 .. 2^31 - 1 or None
-    (the map's peak, read on the device); alpha_max 0 .. 256, floor 0 .. 255.  Shapes, types and ranges raise
-    ValueError before anything is asked of a device."""
-    who = 'draw_heat'
-    if kind not in ('nv12', 'bgr'):
-        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
-    items = list(items)
-    if not items:
-        raise ValueError(f'{who}: no surface')
-    if any(not (isinstance(it, (tuple, list)) and len(it) == 4) for it in items):
-        raise ValueError(f'{who}: an item is (surface, width, camera, table)')
-    if source not in HEAT_SOURCES:
-        raise ValueError(f'{who}: source is one of {", ".join(HEAT_SOURCES)}, got {source!r}')
-    for name, v, lo, hi in (('alpha_max', alpha_max, 0, 256), ('floor', floor, 0, 255)):
-        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-            raise ValueError(f'{who}: {name} is an integer in {lo} .. {hi}, got {v!r}')
-    if full_scale is not None and (isinstance(full_scale, bool) or not isinstance(full_scale, int)
-                                   or not 1 <= full_scale <= 2 ** 31 - 1):
-        raise ValueError(f'{who}: full_scale is None or an integer in 1 .. 2^31 - 1, got {full_scale!r}')
-    cameras, _, Gw, Gh = _heat_state(who, state, ('peak', 'dwell', 'visits'), size, cell)
-    if not (isinstance(palette, torch.Tensor) and palette.dtype == torch.uint8 and palette.dim() == 3
-            and 1 <= palette.shape[0] <= native.HEAT_MAX_TABLES and tuple(palette.shape[1:]) == (256, 3)
-            and palette.is_contiguous()):
-        raise ValueError(f'{who}: palette is a contiguous uint8 [1 .. {native.HEAT_MAX_TABLES}, 256, 3] tensor')
-    tables = palette.shape[0]
+def _camera_surfaces(who, kind, items, cameras, tables):
+    """The (pitch, W, H, camera, table) of every (surface, width, camera, table) item of a draw call that reads a
+    monitor's state, or the ValueError."""
     geometry = []
     for i, (surf, width, camera, table) in enumerate(items):
         if not (isinstance(surf, torch.Tensor) and surf.dtype == torch.uint8):
@@ -1553,6 +1532,41 @@ def draw_heat(kind, items, state, palette, *, size, cell=8, source='dwell', full
         if isinstance(table, bool) or not isinstance(table, numbers.Integral) or not 0 <= table < tables:
             raise ValueError(f'{who}: surface {i} names palette table {table} of {tables}')
         geometry.append((int(pitch), int(W), int(H), int(camera), int(table)))
+    return geometry
+
+
+def draw_heat(kind, items, state, palette, *, size, cell=8, source='dwell', full_scale=None, alpha_max=160, floor=1,
+              smooth=True):
+    """A footfall map blended into surfaces in place, one launch per 32 surfaces (pave_draw_heat_nv12 / _bgr; the rule
+    is DESIGN section 21).  kind 'nv12' | 'bgr' and a surface as in draw_zones.  items: one (surface, width, camera,
+    table) per surface.  state: the map's int32 device tensors dwell, visits [cameras, Gh, Gw] and peak [cameras, 2],
+    read only.  palette: a uint8 device tensor [tables, 256, 3], 1 .. 8 tables of the 256 colours by level, stored or
+    blended as they are.  size, cell: the map's; source 'dwell' | 'visits'; full_scale an integer 1 .. 2^31 - 1 or None
+    (the map's peak, read on the device); alpha_max 0 .. 256, floor 0 .. 255.  Shapes, types and ranges raise
+    ValueError before anything is asked of a device."""
+    who = 'draw_heat'
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
+    items = list(items)
+    if not items:
+        raise ValueError(f'{who}: no surface')
+    if any(not (isinstance(it, (tuple, list)) and len(it) == 4) for it in items):
+        raise ValueError(f'{who}: an item is (surface, width, camera, table)')
+    if source not in HEAT_SOURCES:
+        raise ValueError(f'{who}: source is one of {", ".join(HEAT_SOURCES)}, got {source!r}')
+    for name, v, lo, hi in (('alpha_max', alpha_max, 0, 256), ('floor', floor, 0, 255)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} is an integer in {lo} .. {hi}, got {v!r}')
+    if full_scale is not None and (isinstance(full_scale, bool) or not isinstance(full_scale, int)
+                                   or not 1 <= full_scale <= 2 ** 31 - 1):
+        raise ValueError(f'{who}: full_scale is None or an integer in 1 .. 2^31 - 1, got {full_scale!r}')
+    cameras, _, Gw, Gh = _heat_state(who, state, ('peak', 'dwell', 'visits'), size, cell)
+    if not (isinstance(palette, torch.Tensor) and palette.dtype == torch.uint8 and palette.dim() == 3
+            and 1 <= palette.shape[0] <= native.HEAT_MAX_TABLES and tuple(palette.shape[1:]) == (256, 3)
+            and palette.is_contiguous()):
+        raise ValueError(f'{who}: palette is a contiguous uint8 [1 .. {native.HEAT_MAX_TABLES}, 256, 3] tensor')
+    tables = palette.shape[0]
+    geometry = _camera_surfaces(who, kind, items, cameras, tables)
     # the shapes are right: now where the tensors live
     dev = state['peak'].device
     if dev.type != 'cuda':
@@ -1577,7 +1591,155 @@ def draw_heat(kind, items, state, palette, *, size, cell=8, source='dwell', full
         _launch(entry, who, dev, ctypes.byref(plan))
 
 
-_REID_STATE = (('person', 1), ('track', 1), ('last', 1), ('hits', 2), ('hist', 3), ('frame', 0), ('next', 0),
+_TRAIL_STATE = (('id', 1), ('last', 1), ('pos', 2), ('head', 1), ('count', 1), ('box', 3), ('pts', 4), ('when', 5),
+                ('frame', 0), ('dropped', 0))
+# name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 4], 4 [cameras, S, L, 2], 5 [cameras, S, L]
+
+
+def _trail_state(who, state, names):
+    """The shapes of the trails' tensors `names` of _TRAIL_STATE -> (cameras, S, L)."""
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name in names):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(names)}')
+    if state['when'].dim() != 3:
+        raise ValueError(f'{who}: state when must be [cameras, S, L], got {tuple(state["when"].shape)}')
+    cameras, S, L = state['when'].shape
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS
+            and 1 <= L <= native.TRAIL_MAX_POINTS):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS}, S in 1 .. {native.TRACK_MAX_TRACKS} and L in '
+                         f'1 .. {native.TRAIL_MAX_POINTS}, got {cameras}, {S} and {L}')
+    for name, kind in _TRAIL_STATE:
+        if name not in names:
+            continue
+        t = state[name]
+        want = ((cameras,), (cameras, S), (cameras, S, 2), (cameras, S, 4), (cameras, S, L, 2), (cameras, S, L))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    return cameras, S, L
+
+
+def _int_in(who, name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
+
+
+def trail_update(entries, state, *, K, stride=1, min_step=16, max_age=30, anchor='feet', anchor_kpts=(), score_thr=0.3,
+                 kpt_thr=0.):
+    """Track trails from frames of tracked poses, one launch per 32 frames (pave_trail_update; the rule is DESIGN
+    section 22).  entries: what `zone_events` takes, one (kpts, bboxes, keep, ids, camera, (sx, sy)) per frame, the
+    frames of one camera in time order; state: int32 device tensors id, last, head, count [cameras, S], pos [cameras,
+    S, 2], box [cameras, S, 4], pts [cameras, S, L, 2], when [cameras, S, L] and frame, dropped [cameras], read and
+    written (L 1 .. 64 is the ring's length); stride 1 .. 255 frames and min_step 0 .. 65535 eighths of a pixel between
+    two committed points; anchor and anchor_kpts as in `zone_events`.  Returns one dict(count [N], span [N], dist [N],
+    path [N]) of new int32 tensors per entry.  Shapes, types and ranges raise ValueError before anything is asked of a
+    device."""
+    who = 'trail_update'
+    entries = list(entries)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= native.TRACK_MAX_K:
+        raise ValueError(f'{who}: K must be an integer in 1 .. {native.TRACK_MAX_K}, got {K!r}')
+    cameras, S, L = _trail_state(who, state, [n for n, _ in _TRAIL_STATE])
+    _int_in(who, 'stride', stride, 1, native.TRAIL_MAX_STRIDE)
+    _int_in(who, 'min_step', min_step, 0, native.TRAIL_MAX_STEP)
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    if anchor not in ZONE_ANCHORS:
+        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
+    anchor_kpts = list(anchor_kpts)
+    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
+            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
+        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
+                         f'{anchor_kpts!r}')
+    checked = _tracked_entries(who, entries, K, cameras)
+    # the shapes are right: now where the tensors live
+    dev = state['when'].device
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n, _ in _TRAIL_STATE):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if any(t is not None and t.device != dev for t in c[:4]):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    names = ('count', 'span', 'dist', 'path')
+    outs = [{n: torch.empty((c[7],), dtype=torch.int32, device=dev) for n in names} for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.TrailPlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
+            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+                _ptr(keep) or None, _ptr(ids) or None
+            out = outs[at + i]
+            plan.out_count[i], plan.out_span[i], plan.out_dist[i], plan.out_path[i] = (out[n].data_ptr() or None
+                                                                                       for n in names)
+            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+        (plan.slot_id, plan.slot_last, plan.slot_pos, plan.slot_head, plan.slot_count, plan.slot_box, plan.pts, plan.when,
+         plan.frame, plan.dropped) = (state[n].data_ptr() for n, _ in _TRAIL_STATE)
+        for i, k in enumerate(anchor_kpts):
+            plan.anchor_kpt[i] = k
+        plan.entries, plan.cameras, plan.S, plan.K, plan.L = len(part), cameras, S, K, L
+        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
+        plan.stride, plan.min_step, plan.max_age = stride, min_step, int(max_age)
+        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        _launch('pave_trail_update', who, dev, ctypes.byref(plan))
+    return outs
+
+
+def draw_trails(kind, items, state, palettes, *, thickness=3, thickness_tail=1, head_radius=0, tail_frames=None,
+                linger=None):
+    """Track trails drawn into surfaces in place, one launch per 32 surfaces (pave_draw_trails_nv12 / _bgr; the rule is
+    DESIGN section 22).  kind 'nv12' | 'bgr' and a surface as in draw_zones.  items: one (surface, width, camera, table)
+    per surface.  state: the trails' int32 device tensors (all of `trail_update`'s but dropped), read only.  palettes: 1
+    .. 4 tables of 96 bytes, the 32 colours as they are stored: (Y, U, V) or (B, G, R); a track takes row (id - 1) % 32.
+    thickness, thickness_tail 1 .. 32 pixels at the newest and the oldest end (thickness_tail <= thickness); head_radius
+    0 .. 32; tail_frames None or 1 .. 2^30; linger None or 0 .. 2^30.  Shapes, types and ranges raise ValueError before
+    anything is asked of a device."""
+    who = 'draw_trails'
+    if kind not in ('nv12', 'bgr'):
+        raise ValueError(f"{who}: kind {kind!r} is not 'nv12' or 'bgr'")
+    items = list(items)
+    if not items:
+        raise ValueError(f'{who}: no surface')
+    if any(not (isinstance(it, (tuple, list)) and len(it) == 4) for it in items):
+        raise ValueError(f'{who}: an item is (surface, width, camera, table)')
+    _int_in(who, 'thickness', thickness, 1, native.TRAIL_MAX_THICKNESS)
+    _int_in(who, 'thickness_tail', thickness_tail, 1, thickness)
+    _int_in(who, 'head_radius', head_radius, 0, native.TRAIL_MAX_RADIUS)
+    if tail_frames is not None:
+        _int_in(who, 'tail_frames', tail_frames, 1, native.TRAIL_MAX_FRAMES)
+    if linger is not None:
+        _int_in(who, 'linger', linger, 0, native.TRAIL_MAX_FRAMES)
+    names = [n for n, _ in _TRAIL_STATE if n != 'dropped']
+    cameras, S, L = _trail_state(who, state, names)
+    palettes = list(palettes)
+    if not 1 <= len(palettes) <= native.DRAW_MAX_TABLES or any(
+            not isinstance(p, (bytes, bytearray)) or len(p) != 3 * native.DRAW_PALETTE for p in palettes):
+        raise ValueError(f'{who}: palettes are 1 .. {native.DRAW_MAX_TABLES} tables of {3 * native.DRAW_PALETTE} bytes')
+    geometry = _camera_surfaces(who, kind, items, cameras, len(palettes))
+    # the shapes are right: now where the tensors live
+    dev = state['when'].device
+    if dev.type != 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n in names):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, it in enumerate(items):
+        if it[0].device != dev:
+            raise ValueError(f"{who}: surface {i} is on {it[0].device}, the trails on {dev}")
+    entry = 'pave_draw_trails_nv12' if kind == 'nv12' else 'pave_draw_trails_bgr'
+    for at in range(0, len(items), native.DRAW_MAX_SURFACES):
+        plan = native.TrailDrawPlan()
+        part = items[at:at + native.DRAW_MAX_SURFACES]
+        for i, it in enumerate(part):
+            plan.dst[i] = it[0].data_ptr()
+            plan.pitch[i], plan.width[i], plan.height[i], plan.camera[i], plan.table[i] = geometry[at + i]
+        (plan.slot_id, plan.slot_last, plan.slot_pos, plan.slot_head, plan.slot_count, plan.slot_box, plan.pts, plan.when,
+         plan.frame) = (state[n].data_ptr() for n in names)
+        for t, p in enumerate(palettes):
+            ctypes.memmove(plan.palette[t], bytes(p), len(p))
+        plan.n, plan.cameras, plan.S, plan.L = len(part), cameras, S, L
+        plan.thickness, plan.thickness_tail, plan.head_radius = thickness, thickness_tail, head_radius
+        plan.tail_frames, plan.linger = 0 if tail_frames is None else tail_frames, -1 if linger is None else linger
+        _launch(entry, who, dev, ctypes.byref(plan))
+
+
+_REID_STATE =(('person', 1), ('track', 1), ('last', 1), ('hits', 2), ('hist', 3), ('frame', 0), ('next', 0),
                ('dropped', 0))   # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 2, 256]
 
 
