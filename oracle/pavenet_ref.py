@@ -550,7 +550,7 @@ def gen_encoder_output_proposals(sd, pre, memory, memory_padding_mask, spatial_s
 # encoder (hot loop #1): DetrTransformerEncoder of BaseTransformerLayer
 # ('self_attn','norm','ffn','norm')  MT:501-531, BT:1253-1353
 # --------------------------------------------------------------------------
-def encoder_forward(sd, pre, num_layers, feat, pos, mask, reference_points, shapes, lsi):
+def encoder_forward(sd, pre, num_layers, feat, pos, mask, reference_points, shapes, lsi, taps=None):
     x = feat
     for i in range(num_layers):
         lp = f'{pre}.layers.{i}'
@@ -558,6 +558,8 @@ def encoder_forward(sd, pre, num_layers, feat, pos, mask, reference_points, shap
         x = layer_norm(sd, lp + '.norms.0', x)
         x = ffn(sd, lp + '.ffns.0', x)
         x = layer_norm(sd, lp + '.norms.1', x)
+        if taps is not None:
+            taps.setdefault('memory_layers', []).append(x)  # [S, B*T, C] after layer i
     return x
 
 
@@ -591,7 +593,7 @@ def videopose_transformer_forward(sd, hpre, cfg, mlvl_feats, mlvl_masks, mlvl_po
         sd, tpre, mlvl_feats, mlvl_masks, mlvl_pos)
     reference_points = get_reference_points(shapes, valid_ratios)
     memory = encoder_forward(sd, tpre + '.encoder', n_enc, feat_f.permute(1, 0, 2),
-                             pos_f.permute(1, 0, 2), mask_f, reference_points, shapes, lsi)
+                             pos_f.permute(1, 0, 2), mask_f, reference_points, shapes, lsi, taps=taps)
     memory = memory.permute(1, 0, 2)  # [B*T, S, C]
     bs, _, c = memory.shape
     if taps is not None:

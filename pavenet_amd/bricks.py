@@ -918,8 +918,10 @@ class BaseTransformerLayer(BaseModule):
                     fuse = dict(fuse, out=layer_out)
                 query = self.ffns[ffn_index](query, identity if self.pre_norm else None, **fuse)
                 ffn_index += 1
-            skip_norm = bool(fuse)
-            if fuse:
+            # (only a module that was HANDED the LayerNorm has applied it: `inplace_residual` alone -- every encoder
+            # layer off the device -- is no reason to skip the norm)
+            skip_norm = fuse.get('post_norm') is not None
+            if skip_norm:
                 identity = query
         return query
 

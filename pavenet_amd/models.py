@@ -53,7 +53,7 @@ def videopose_r50_cfg(num_frames=3, num_keypoints=15, num_query=300, max_per_img
             with_kpt_refine=True, as_two_stage=True,
             transformer=dict(
                 type='opera.VideoPoseTransformerMulFrames', num_keypoints=num_keypoints,
-                num_frames=T,
+                num_frames=T, two_stage_num_proposals=num_query,   # (one proposal per query embedding row)
                 encoder=dict(
                     type='mmcv.DetrTransformerEncoder', num_layers=enc_layers,
                     transformerlayers=dict(
