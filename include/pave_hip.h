@@ -1181,6 +1181,72 @@ int pave_draw_trails_nv12(const pave_trail_draw_plan* plan, void* stream);
 int pave_draw_trails_bgr(const pave_trail_draw_plan* plan, void* stream);
 
 /*
+ * The ground plane: every pose's position on the floor in millimetres through a calibrated homography, its track's
+ * speed and distance walked, its nearest neighbour, and the poses restated in floor units for the anchor-based
+ * consumers (pavenet_amd/csrc/pave_floor.hip; the rule is DESIGN section 23, integer-exact).  The plan is copied
+ * into the kernel's arguments.
+ *
+ * pave_floor_update: one launch for `entries` frames of any of `cameras` cameras; one block per camera of the launch
+ * takes that camera's entries in plan order, as pave_zone_events does: entries of one camera are in time order.
+ *   kpts[i], bboxes[i], keep[i], ids[i], n[i], camera[i], scale[i], anchor, anchor_kpt, n_anchor, S, K, max_age,
+ *   score_thr, kpt_thr   as in pave_zone_plan: the same 1/8-pixel anchor (ax, ay)
+ *   calib            DEVICE [cameras, PAVE_FLOOR_CALIB_WORDS] int64, read: words 0 .. 8 the matrix G row by row (1/8
+ *                    pixel -> floor, times a power of two; every row has (|g0| + |g1|) 65535 + |g2| < 2^61), words 9 ..
+ *                    12 the bounds x0, y0, x1, y1 in mm (read clamped to +-PAVE_FLOOR_MAX_MM), word 13 != 0: the
+ *                    camera is calibrated.  With n = G (ax, ay, 1): on the floor iff n2 > 0 and X = floor((2 n0 + n2)
+ *                    / (2 n2)), Y likewise lie in the bounds, ends included
+ *   out[i]           DEVICE [PAVE_FLOOR_OUT_WORDS * n[i]] int32, out: on [n], xy [n, 2] (mm), vel [n, 2], speed [n]
+ *                    (1/256 mm per frame), travel [n] (mm), nearest [n] (a pose index or -1), gap [n] (mm or -1), near
+ *                    [n], one after the other
+ *   out_floor[i]     DEVICE [n[i] * K * 3 + n[i] * 5] float, out: the key points, then the boxes, of the result in
+ *                    floor units: with P = floor(4 (X - origin) / unit) per axis in 0 .. 32767 every x and y is P / 4,
+ *                    else NaN; the scores are copied (both may be NULL where n[i] == 0)
+ *   the state, DEVICE int32, read and written: slot_id, slot_last, slot_hits, slot_travel [cameras, S] (id 0: a free
+ *                    slot, its other fields are never read), slot_pos (mm), slot_vel (1/256 mm per frame) [cameras,
+ *                    S, 2]; frame, dropped [cameras]
+ *   velocity_gain    1 .. 16: sixteenths of the newest move that go into the velocity
+ *   near             0 .. 2^20 mm: neighbours at most this far are counted
+ *   unit             1 .. 1000 mm per floor pixel;  origin_x, origin_y: +-PAVE_FLOOR_MAX_MM, the plan's corner in mm
+ * Refused with PAVE_E_ARG before any device call: whatever pave_zone_events refuses in the fields of the same name, a
+ * null state, calibration or output tensor, velocity_gain outside 1 .. 16, near outside 0 .. 2^20, unit outside 1 ..
+ * 1000, an origin outside +-(2^20 - 1).  A slot index is a loop counter and a pose index is below n[i]: a plan that
+ * passes cannot address memory outside its tensors, whatever the poses, the state and the calibration hold.
+ */
+#define PAVE_FLOOR_CALIB_WORDS 16
+#define PAVE_FLOOR_CALIB_BOUNDS 9
+#define PAVE_FLOOR_CALIB_VALID 13
+#define PAVE_FLOOR_OUT_WORDS 10
+#define PAVE_FLOOR_MAX_MM 1048575
+#define PAVE_FLOOR_MAX_NEAR 1048576
+#define PAVE_FLOOR_MAX_UNIT 1000
+#define PAVE_FLOOR_MAX_GAIN 16
+#define PAVE_FLOOR_MAX_HITS 1073741824
+typedef struct pave_floor_plan {
+  const float*   kpts[PAVE_TRACK_MAX_FRAMES];
+  const float*   bboxes[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* keep[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out[PAVE_TRACK_MAX_FRAMES];
+  float*         out_floor[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  float          scale[PAVE_TRACK_MAX_FRAMES][2];
+  int32_t* slot_id;
+  int32_t* slot_last;
+  int32_t* slot_hits;
+  int32_t* slot_pos;
+  int32_t* slot_vel;
+  int32_t* slot_travel;
+  int32_t* frame;
+  int32_t* dropped;
+  const int64_t* calib;
+  int anchor_kpt[PAVE_ZONE_MAX_ANCHOR_KPTS];
+  int entries, cameras, S, K, anchor, n_anchor, velocity_gain, near, unit, origin_x, origin_y, max_age;
+  float score_thr, kpt_thr;
+} pave_floor_plan;
+int pave_floor_update(const pave_floor_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

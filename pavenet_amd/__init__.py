@@ -59,6 +59,9 @@ def __getattr__(name):
     if name in ('TrackTrails', 'TrailStyle', 'draw_trails_nv12', 'draw_trails_bgr'):
         from . import trails
         return getattr(trails, name)
+    if name == 'GroundPlane':
+        from . import floor
+        return floor.GroundPlane
     if name == 'PersonReID':
         from . import reid
         return reid.PersonReID

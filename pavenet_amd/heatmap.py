@@ -15,8 +15,9 @@ which it could pass 2^31 is 2^31 / (128 (radius + 1)^2) -- 1 048 576 frames at r
 per second with 128 people on one cell), 4 194 304 at radius 1 -- and ``reset`` is the remedy; with a half life of at
 most 2^18 frames no cell can get there.
 
-Not built: maps on the ground plane (a homography), per-hour maps or export formats, Gaussian footprints, anti-aliased
-colour ramps with text legends.  (The path of one track is ``trails.TrackTrails``.)
+Not built: per-hour maps or export formats, Gaussian footprints, anti-aliased colour ramps with text legends.  (The path
+of one track is ``trails.TrackTrails``.  A map on the ground plane is this map fed with ``floor.GroundPlane``'s
+``out['floor']``)
 """
 import numpy as np
 import torch

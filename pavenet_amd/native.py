@@ -361,6 +361,28 @@ class TrailDrawPlan(ctypes.Structure):
                 ('thickness_tail', ctypes.c_int), ('head_radius', ctypes.c_int), ('tail_frames', ctypes.c_int),
                 ('linger', ctypes.c_int)]
 
+FLOOR_CALIB_WORDS, FLOOR_CALIB_BOUNDS, FLOOR_CALIB_VALID, FLOOR_OUT_WORDS = (
+    DEFINES['PAVE_FLOOR_' + n] for n in ('CALIB_WORDS', 'CALIB_BOUNDS', 'CALIB_VALID', 'OUT_WORDS'))
+FLOOR_MAX_MM, FLOOR_MAX_NEAR, FLOOR_MAX_UNIT, FLOOR_MAX_GAIN, FLOOR_MAX_HITS = (
+    DEFINES['PAVE_FLOOR_MAX_' + n] for n in ('MM', 'NEAR', 'UNIT', 'GAIN', 'HITS'))
+
+
+class FloorPlan(ctypes.Structure):
+    """`pave_floor_plan` of include/pave_hip.h (the by-value argument of pave_floor_update)."""
+    _fields_ = [('kpts', ctypes.c_void_p * TRACK_MAX_FRAMES), ('bboxes', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('keep', ctypes.c_void_p * TRACK_MAX_FRAMES), ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out_floor', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('n', ctypes.c_int * TRACK_MAX_FRAMES), ('camera', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('scale', (ctypes.c_float * 2) * TRACK_MAX_FRAMES), ('slot_id', ctypes.c_void_p),
+                ('slot_last', ctypes.c_void_p), ('slot_hits', ctypes.c_void_p), ('slot_pos', ctypes.c_void_p),
+                ('slot_vel', ctypes.c_void_p), ('slot_travel', ctypes.c_void_p), ('frame', ctypes.c_void_p),
+                ('dropped', ctypes.c_void_p), ('calib', ctypes.c_void_p),
+                ('anchor_kpt', ctypes.c_int * ZONE_MAX_ANCHOR_KPTS), ('entries', ctypes.c_int),
+                ('cameras', ctypes.c_int), ('S', ctypes.c_int), ('K', ctypes.c_int), ('anchor', ctypes.c_int),
+                ('n_anchor', ctypes.c_int), ('velocity_gain', ctypes.c_int), ('near', ctypes.c_int),
+                ('unit', ctypes.c_int), ('origin_x', ctypes.c_int), ('origin_y', ctypes.c_int),
+                ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
+
 
 _lib = None
 

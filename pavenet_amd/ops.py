@@ -1739,6 +1739,101 @@ def draw_trails(kind, items, state, palettes, *, thickness=3, thickness_tail=1, 
         _launch(entry, who, dev, ctypes.byref(plan))
 
 
+_FLOOR_STATE = (('id', 1), ('last', 1), ('hits', 1), ('pos', 2), ('vel', 2), ('travel', 1), ('frame', 0), ('dropped', 0))
+# name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2]
+FLOOR_OUTPUTS = (('on', 1), ('xy', 2), ('vel', 2), ('speed', 1), ('travel', 1), ('nearest', 1), ('gap', 1), ('near', 1))
+# name, words per pose: the sections of one launch output, one after the other
+
+
+def floor_update(entries, state, calib, *, K, velocity_gain=4, near=1500, unit=10, origin=(0, 0), max_age=30,
+                 anchor='feet', anchor_kpts=(), score_thr=0.3, kpt_thr=0.):
+    """Floor positions, speeds and neighbours from frames of tracked poses, one launch per 32 frames
+    (pave_floor_update; the rule is DESIGN section 23).  entries: what `zone_events` takes, one (kpts, bboxes, keep,
+    ids, camera, (sx, sy)) per frame, the frames of one camera in time order; state: int32 device tensors id, last,
+    hits, travel [cameras, S], pos, vel [cameras, S, 2] and frame, dropped [cameras], read and written; calib: the int64
+    [cameras, 16] device tensor of the calibrations, read; velocity_gain 1 .. 16, near 0 .. 2^20 mm, unit 1 .. 1000 mm
+    per floor pixel, origin (x, y) in mm within +-(2^20 - 1); anchor and anchor_kpts as in `zone_events`.  Returns one
+    dict per entry of new tensors: int32 on, speed, travel, nearest, gap, near [N] and xy, vel [N, 2], and float32 kpts
+    [N, K, 3] and bboxes [N, 5], the poses in floor units.  Shapes, types and ranges raise ValueError before anything
+    is asked of a device."""
+    who = 'floor_update'
+    entries = list(entries)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= native.TRACK_MAX_K:
+        raise ValueError(f'{who}: K must be an integer in 1 .. {native.TRACK_MAX_K}, got {K!r}')
+    names = [n for n, _ in _FLOOR_STATE]
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name in names):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(names)}')
+    if state['id'].dim() != 2:
+        raise ValueError(f'{who}: state id must be [cameras, S], got {tuple(state["id"].shape)}')
+    cameras, S = state['id'].shape
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS} and S in 1 .. {native.TRACK_MAX_TRACKS}, got '
+                         f'{cameras} and {S}')
+    for name, kind in _FLOOR_STATE:
+        t, want = state[name], ((cameras,), (cameras, S), (cameras, S, 2))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    if not (isinstance(calib, torch.Tensor) and calib.dtype == torch.int64 and calib.is_contiguous()
+            and tuple(calib.shape) == (cameras, native.FLOOR_CALIB_WORDS)):
+        raise ValueError(f'{who}: calib must be a contiguous int64 [{cameras}, {native.FLOOR_CALIB_WORDS}] tensor')
+    _int_in(who, 'velocity_gain', velocity_gain, 1, native.FLOOR_MAX_GAIN)
+    _int_in(who, 'near', near, 0, native.FLOOR_MAX_NEAR)
+    _int_in(who, 'unit', unit, 1, native.FLOOR_MAX_UNIT)
+    if not (isinstance(origin, (tuple, list)) and len(origin) == 2):
+        raise ValueError(f'{who}: origin is (x, y) in mm, got {origin!r}')
+    for v in origin:
+        _int_in(who, 'origin', v, -native.FLOOR_MAX_MM, native.FLOOR_MAX_MM)
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    if anchor not in ZONE_ANCHORS:
+        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
+    anchor_kpts = list(anchor_kpts)
+    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
+            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
+        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
+                         f'{anchor_kpts!r}')
+    checked = _tracked_entries(who, entries, K, cameras)
+    # the shapes are right: now where the tensors live
+    dev = state['id'].device
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n in names) or calib.device != dev:
+        raise ValueError(f'{who}: the state tensors and calib must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if any(t is not None and t.device != dev for t in c[:4]):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    words = [torch.empty((native.FLOOR_OUT_WORDS * c[7],), dtype=torch.int32, device=dev) for c in checked]
+    floats = [torch.empty((c[7] * (K * 3 + 5),), dtype=torch.float32, device=dev) for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.FloorPlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
+            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+                _ptr(keep) or None, _ptr(ids) or None
+            plan.out[i], plan.out_floor[i] = words[at + i].data_ptr() or None, floats[at + i].data_ptr() or None
+            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+        (plan.slot_id, plan.slot_last, plan.slot_hits, plan.slot_pos, plan.slot_vel, plan.slot_travel, plan.frame,
+         plan.dropped) = (state[n].data_ptr() for n in names)
+        plan.calib = calib.data_ptr()
+        for i, k in enumerate(anchor_kpts):
+            plan.anchor_kpt[i] = k
+        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
+        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
+        plan.velocity_gain, plan.near, plan.unit, plan.max_age = velocity_gain, near, unit, int(max_age)
+        plan.origin_x, plan.origin_y = origin
+        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        _launch('pave_floor_update', who, dev, ctypes.byref(plan))
+    outs = []
+    for c, w, f in zip(checked, words, floats):
+        N, at, out = c[7], 0, {}
+        for name, per in FLOOR_OUTPUTS:
+            out[name] = w[at:at + per * N].view((N,) if per == 1 else (N, per))
+            at += per * N
+        out['kpts'], out['bboxes'] = f[:N * K * 3].view(N, K, 3), f[N * K * 3:].view(N, 5)
+        outs.append(out)
+    return outs
+
+
 _REID_STATE =(('person', 1), ('track', 1), ('last', 1), ('hits', 2), ('hist', 3), ('frame', 0), ('next', 0),
                ('dropped', 0))   # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 2, 256]
 

@@ -17,8 +17,8 @@ at the old end.  In the loop the trails go over the zones and under the skeleton
 The outputs per pose -- count, span, dist, path -- give a mean speed (dist / span, 1/8 pixel per frame) and tell a walk
 from a wander (path / dist).
 
-Not built: trails on the ground plane (a homography), per-key-point trails, anti-aliasing or alpha fades, export
-formats.
+Not built: per-key-point trails, anti-aliasing or alpha fades, export formats.  (Trails on the ground plane are these
+trails fed with ``floor.GroundPlane``'s ``out['floor']``)
 """
 import numpy as np
 import torch

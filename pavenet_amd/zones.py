@@ -11,7 +11,8 @@ figure.
 
 ``overlay.draw_zones_nv12`` / ``draw_zones_bgr`` draw the zones, the lines and these counters into the picture.
 
-Not built: a hysteresis band for lines, zones in ground-plane coordinates, per-id exemptions in ``anonymize``.
+Not built: a hysteresis band for lines, per-id exemptions in ``anonymize``.  (Zones in ground-plane coordinates are
+zones drawn on the plan and fed with ``floor.GroundPlane``'s ``out['floor']``)
 """
 import math
 
