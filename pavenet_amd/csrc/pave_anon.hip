@@ -36,23 +36,17 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
 
+using pave_tracked::QMAX;
+using pave_tracked::quant;
+
 constexpr int TILE = PAVE_ANON_MAX_CELL;          // pixels per tile edge
-constexpr int QMAX = 32767;                       // the largest quarter-pixel coordinate
 constexpr int MAX_CELLS = (TILE / 2) * (TILE / 2);   // cells of a tile at cell = 2
 
 struct Region { int x1, y1, x2, y2, r; };         // quarter pixels
-
-// A coordinate in quarter pixels (the function of pave_draw.hip: the clamp is made in float, where it is defined for
-// an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 __device__ __forceinline__ bool finite4(const float a, const float b, const float c, const float d) {
   return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);

@@ -37,11 +37,14 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
 
+using pave_tracked::QMAX;
+using pave_tracked::quant;
+
 constexpr int TILE = 32;        // pixels per tile edge
-constexpr int QMAX = 32767;     // the largest quarter-pixel coordinate
 
 struct Prim {                   // one candidate of the tile's list
   short ax, ay, bx, by;
@@ -59,15 +62,6 @@ template <int IDS> struct DrawTypes { using plan = pave_draw_plan; using prim = 
 template <> struct DrawTypes<1> { using plan = pave_draw_ids_plan; using prim = PrimIds; };
 __device__ __forceinline__ const pave_draw_plan& base_of(const pave_draw_plan& p) { return p; }
 __device__ __forceinline__ const pave_draw_plan& base_of(const pave_draw_ids_plan& p) { return p.base; }
-
-// A coordinate in quarter pixels.  The clamp is made in float, where it is the same function for every finite
-// quotient and defined for an infinite one (a finite x over a tiny scale).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 __device__ __forceinline__ bool finite4(const float a, const float b, const float c, const float d) {
   return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);

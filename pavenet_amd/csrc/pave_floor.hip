@@ -4,14 +4,14 @@
 // (pave_floor_update).
 //
 // The rule is DESIGN section 23 and is integer-exact.  A pose stands on section 17's anchor (ax, ay) in 1/8 pixel
-// (pave_zones.hip's quant, its three anchor modes and its fallback to the box).  A camera holds nine int64 words G,
+// (pave_tracked.h: quant, the three anchor modes and the fallback to the box).  A camera holds nine int64 words G,
 // the homography from 1/8 pixel to floor millimetres times a power of two, every row with (|g0| + |g1|) 65535 + |g2|
 // < 2^61, and four bounds in mm.  With
 //   nx = g00 ax + g01 ay + g02,  ny = g10 ax + g11 ay + g12,  w = g20 ax + g21 ay + g22          (|.| < 2^61)
 // the pose is on the floor iff w > 0 and X = floor((2 nx + w) / (2 w)), Y likewise (|2 n + w| < 2^63), lie in the
 // bounds, ends included.  A pose is placed iff keep, a box score above the threshold, finite coordinates and on the
 // floor; it is followed iff it is placed, its id is >= 1, no placed pose before it has that id and it finds or takes a
-// slot (pave_smooth.hip's slots: the clock, the expiry after max_age frames, the serial births of one lane).  A born
+// slot (pave_tracked.h's slots: the clock, the expiry after max_age frames, the serial births of one lane).  A born
 // slot takes pos = (X, Y), vel = 0, travel = 0, hits = 1.  A slot that was there, with dt = frame - last and d = (X, Y)
 // - pos: per axis m = floor(256 d / dt), vel = m when hits == 1, else vel += floor(gain (m - vel) / 16); travel =
 // min(2^31 - 1, travel + isqrt(dx^2 + dy^2)); hits = min(hits + 1, 2^30).  Among the placed poses of the frame pose i's
@@ -19,8 +19,8 @@
 // within `near` mm.  The bridge: P = floor(4 (X - origin) / unit) per axis; with both in 0 .. 32767 every x and y of
 // the pose's key points and box becomes P / 4 (exact in fp32), else NaN; scores are copied.
 //
-// One block of 256 threads per camera of the launch: block b works iff entry b is the first entry of its camera, and
-// then takes that camera's entries in plan order, as zone_events_kernel does.  The calibration goes into LDS once.
+// One block of 256 threads per camera of the launch (pave_tracked.h).  The calibration goes into LDS once.  Its own
+// order: classification, then the projection rewrites det_ok to "placed", and the slot scan runs after that.
 // Per frame thread t < S expires slot t; thread d < N classes pose d, projects it (two 64-bit divisions: a software
 // sequence on this hardware, so the quotients go to LDS as 32-bit words and nothing divides twice) and finds its slot;
 // the N^2 neighbour pass runs over all 256 threads, two per pose, each over half of j (every lane of a wave reads the
@@ -35,32 +35,18 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using namespace pave_tracked;
 
 constexpr int NT = 256;                              // threads of a block
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
 constexpr int MAXS = PAVE_TRACK_MAX_TRACKS;
 constexpr int CW = PAVE_FLOOR_CALIB_WORDS;
-constexpr int QMAX = 32767;                          // the largest quarter-pixel coordinate
-constexpr int NEEDS_BIRTH = -2;
 constexpr long long MM = PAVE_FLOOR_MAX_MM;
 static_assert(2 * MAXP == NT && MAXS <= NT, "thread roles: two threads per pose in the neighbour pass");
-
-// A coordinate in quarter pixels: pave_track.hip's expression (the clamp in float is defined for an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
-
-// floor(a / b) for b > 0: C's / truncates, so a negative remainder steps the quotient down.
-__device__ __forceinline__ long long floor_div(const long long a, const long long b) {
-  long long q = a / b;
-  if (a - q * b < 0) --q;
-  return q;
-}
 
 // floor(sqrt(v)) for v < 2^63.  The double holds v to 53 bits and its square root is rounded once more, so the
 // truncated root is off by one at the most, either way; the two corrections make it the floor.
@@ -95,8 +81,7 @@ __global__ __launch_bounds__(NT) void floor_update_kernel(const pave_floor_plan 
 
   const int b = blockIdx.x;
   const int cam = plan.camera[b];
-  for (int e = 0; e < b; ++e)
-    if (plan.camera[e] == cam) return;   // (block-uniform, before any barrier: an earlier block has this camera)
+  if (!owns_camera(plan, b, cam)) return;   // (block-uniform, before any barrier: an earlier block has this camera)
   const int tid = threadIdx.x;
   const int S = plan.S, K = plan.K;
   int32_t* __restrict__ g_id = plan.slot_id + (long long)cam * S;
@@ -132,55 +117,20 @@ __global__ __launch_bounds__(NT) void floor_update_kernel(const pave_floor_plan 
     const int frame = (int)((unsigned)cam_state[0] + 1u);
 
     // ---- expire the slots; the poses' boxes ----
-    if (tid < MAXS) {
-      int id = 0;
-      if (tid < S) {
-        id = g_id[tid];
-        if (id != 0 && (long long)frame - g_last[tid] > plan.max_age) {
-          id = 0;
-          g_id[tid] = 0;
-        }
-      }
-      slot_id[tid] = id;
-    }
+    if (tid < MAXS) expire_slot(plan, g_id, g_last, slot_id, tid, S, frame);
     int X1 = 0, Y1 = 0, X2 = 0, Y2 = 0;
-    if (tid < n) {
-      const float* bb = bboxes + tid * 5;
-      const float b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
-      X1 = quant(b0, sx), Y1 = quant(b1, sy), X2 = quant(b2, sx), Y2 = quant(b3, sy);
-      det_bad[tid] = isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3) ? 0 : 1;
-      det_ok[tid] = (keep == nullptr || keep[tid] != 0) && bb[4] > plan.score_thr ? 1 : 0;
-      det_id[tid] = ids[tid];
-      det_born[tid] = 0;
-    }
+    if (tid < n)
+      classify_pose(bboxes, keep, ids, sx, sy, plan.score_thr, tid, det_id, det_bad, det_ok, det_born, X1, Y1, X2, Y2);
     __syncthreads();
-    for (int i = tid; i < n * K; i += NT) {
-      const float x = kpts[3 * i], y = kpts[3 * i + 1];
-      if (!(isfinite(x) && isfinite(y))) atomicOr(&det_bad[i / K], 1);
-    }
+    sweep_finite<NT>(kpts, n, K, tid, det_bad);
     __syncthreads();
 
     // ---- the anchor, the projection and the bridge of pose tid: who is placed ----
     if (tid < n) {
       int placed = 0, X = 0, Y = 0, px = -1, py = -1;
       if (det_ok[tid] != 0 && det_bad[tid] == 0 && cal[PAVE_FLOOR_CALIB_VALID] != 0) {
-        long long ax = (long long)X1 + X2, ay = 2ll * Y2;   // the bottom centre of the box
-        if (plan.anchor == PAVE_ZONE_ANCHOR_CENTRE) ay = (long long)Y1 + Y2;
-        if (plan.anchor == PAVE_ZONE_ANCHOR_FEET) {
-          long long sum_x = 0, sum_y = 0, seen = 0;
-          for (int i = 0; i < plan.n_anchor; ++i) {
-            const float* kp = kpts + 3 * (tid * K + plan.anchor_kpt[i]);
-            if (kp[2] > plan.kpt_thr) {
-              sum_x += quant(kp[0], sx);
-              sum_y += quant(kp[1], sy);
-              ++seen;
-            }
-          }
-          if (seen > 0) {   // (sums >= 0: / is floor)
-            ax = 2 * sum_x / seen;
-            ay = 2 * sum_y / seen;
-          }
-        }
+        long long ax, ay;
+        anchor(plan, kpts, tid, K, sx, sy, X1, Y1, X2, Y2, ax, ay);
         const long long nx = cal[0] * ax + cal[1] * ay + cal[2];
         const long long ny = cal[3] * ax + cal[4] * ay + cal[5];
         const long long w = cal[6] * ax + cal[7] * ay + cal[8];
@@ -205,19 +155,8 @@ __global__ __launch_bounds__(NT) void floor_update_kernel(const pave_floor_plan 
     __syncthreads();
 
     // ---- the slot of every pose; the neighbours of pose tid % 128 among half of the poses ----
-    if (tid < n) {
-      const int id = det_id[tid];
-      int slot = -1;
-      if (det_ok[tid] != 0 && id >= 1) {
-        bool first = true;
-        for (int p = 0; p < tid; ++p) first = first && !(det_id[p] == id && det_ok[p] != 0);
-        if (first) {
-          slot = NEEDS_BIRTH;
-          for (int t = S - 1; t >= 0; --t) slot = slot_id[t] == id ? t : slot;   // (the lowest, were there two)
-        }
-      }
-      det_slot[tid] = slot;
-    }
+    if (tid < n)   // (det_ok is "placed" by now, and a placed pose is not bad)
+      det_slot[tid] = find_slot(det_id, det_ok, nullptr, slot_id, tid, S);
     const int pose = tid & (MAXP - 1), upper = tid >> 7;
     unsigned long long best = ~0ull;
     int best_j = -1, close = 0;
@@ -238,26 +177,8 @@ __global__ __launch_bounds__(NT) void floor_update_kernel(const pave_floor_plan 
       nb_near[pose] = close;
     }
     __syncthreads();
-    if (tid == 0) {   // births, in ascending pose index into the lowest free slot
-      int free_t = 0, dropped = cam_state[1];
-      for (int d = 0; d < n; ++d) {
-        if (det_slot[d] != NEEDS_BIRTH) continue;
-        while (free_t < S && slot_id[free_t] != 0) ++free_t;
-        if (free_t < S) {
-          slot_id[free_t] = det_id[d];
-          g_id[free_t] = det_id[d];
-          det_slot[d] = free_t;
-          det_born[d] = 1;
-        } else {
-          det_slot[d] = -1;
-          dropped = (int)((unsigned)dropped + 1u);
-        }
-      }
-      cam_state[0] = frame;
-      cam_state[1] = dropped;
-      plan.frame[cam] = frame;
-      plan.dropped[cam] = dropped;
-    }
+    if (tid == 0)   // births, in ascending pose index into the lowest free slot; the clock
+      commit_births(plan, cam, n, S, frame, true, g_id, slot_id, det_id, det_slot, det_born, cam_state);
     __syncthreads();
 
     // ---- pose tid in its slot; its outputs ----

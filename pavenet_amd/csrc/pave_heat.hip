@@ -4,7 +4,7 @@
 // pitched NV12; pave_draw_heat_bgr: [H, W, 3] BGR).
 //
 // Both rules are DESIGN section 21 and are integer-exact.
-//   update: section 17's poses, slots and 1/8-pixel anchor, unchanged.  Per frame: the clock advances and slots not
+//   update: section 17's poses, slots and 1/8-pixel anchor (pave_tracked.h).  Per frame: the clock advances and slots not
 //     seen for more than max_age frames are freed; every half_life frames both maps and peak are halved (v >> 1);
 //     poses find or take slots; a pose that takes part with its anchor a on the map (0 <= a < 8 size) stands in cell
 //     (a.x >> (3 + log2 cell), a.y >> (3 + log2 cell)) and adds (r + 1 - |dx|)(r + 1 - |dy|) to dwell at the cells
@@ -17,8 +17,8 @@
 //     weights 2 cell - f and f, level = (sum wx wy L + 2 cell^2) >> (2 + 2 log2 cell).  a = level < floor ? 0 :
 //     (alpha_max level + 128) >> 8 and out = (src (256 - a) + palette[level] a + 128) >> 8 per byte.
 //
-// Update: pave_zones.hip's scheme, one block of 256 threads per camera of the launch, which takes that camera's entries
-// in plan order, so the forget pass of a frame runs between the splats of the frame before and of its own frame, with a
+// Update: one block of 256 threads per camera of the launch (pave_tracked.h), which takes that camera's entries in
+// plan order, so the forget pass of a frame runs between the splats of the frame before and of its own frame, with a
 // block barrier on either side; launches on one stream follow each other.  The splat is global integer atomics, which
 // commute: 128 poses on one cell come out exact.  An atomic add returns the word before it, so the largest (returned +
 // added) over a frame's adds is the largest word the frame touched, and peak is maintained through an LDS atomic max
@@ -39,25 +39,18 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using namespace pave_tracked;
 
 constexpr int NT = 256;                              // threads of a block
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
 constexpr int MAXS = PAVE_TRACK_MAX_TRACKS;
-constexpr int QMAX = 32767;                          // the largest quarter-pixel coordinate
-constexpr int NEEDS_BIRTH = -2;
 constexpr int TILE = 32;                             // pixels per tile edge of the draw kernels
 constexpr int MAXC = TILE / 4 + 2;                   // cells a tile spans per axis at cell 4, with the ring
 static_assert(MAXP <= NT && MAXS <= NT && MAXC * MAXC <= NT, "thread roles");
-
-// A coordinate in quarter pixels: pave_track.hip's expression (the clamp in float is defined for an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 __device__ __forceinline__ int map_load(const int32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -81,8 +74,7 @@ __global__ __launch_bounds__(NT) void heat_update_kernel(const pave_heat_plan pl
 
   const int b = blockIdx.x;
   const int cam = plan.camera[b];
-  for (int e = 0; e < b; ++e)
-    if (plan.camera[e] == cam) return;   // (block-uniform, before any barrier: an earlier block has this camera)
+  if (!owns_camera(plan, b, cam)) return;   // (block-uniform, before any barrier: an earlier block has this camera)
   const int tid = threadIdx.x;
   const int S = plan.S, K = plan.K;
   const int lc = log2_cell(plan.cell), r = plan.radius;
@@ -112,27 +104,10 @@ __global__ __launch_bounds__(NT) void heat_update_kernel(const pave_heat_plan pl
     const int frame = (int)((unsigned)cam_state[0] + 1u);
 
     // ---- 1: expire the slots; the poses' boxes ----
-    if (tid < MAXS) {
-      int id = 0;
-      if (tid < S) {
-        id = g_id[tid];
-        if (id != 0 && (long long)frame - g_last[tid] > plan.max_age) {
-          id = 0;
-          g_id[tid] = 0;
-        }
-      }
-      slot_id[tid] = id;
-    }
+    if (tid < MAXS) expire_slot(plan, g_id, g_last, slot_id, tid, S, frame);
     int X1 = 0, Y1 = 0, X2 = 0, Y2 = 0;
-    if (tid < n) {
-      const float* bb = bboxes + tid * 5;
-      const float b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
-      X1 = quant(b0, sx), Y1 = quant(b1, sy), X2 = quant(b2, sx), Y2 = quant(b3, sy);
-      det_bad[tid] = isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3) ? 0 : 1;
-      det_ok[tid] = (keep == nullptr || keep[tid] != 0) && bb[4] > plan.score_thr ? 1 : 0;
-      det_id[tid] = ids[tid];
-      det_born[tid] = 0;
-    }
+    if (tid < n)
+      classify_pose(bboxes, keep, ids, sx, sy, plan.score_thr, tid, det_id, det_bad, det_ok, det_born, X1, Y1, X2, Y2);
 
     // ---- 2: forget (the splats of the frame before are behind the barrier at the loop's head) ----
     if (plan.half_life > 0 && frame % plan.half_life == 0) {   // (block-uniform)
@@ -143,47 +118,14 @@ __global__ __launch_bounds__(NT) void heat_update_kernel(const pave_heat_plan pl
       if (tid < 2) peak[tid] >>= 1;
     }
     __syncthreads();
-    for (int i = tid; i < n * K; i += NT) {
-      const float x = kpts[3 * i], y = kpts[3 * i + 1];
-      if (!(isfinite(x) && isfinite(y))) atomicOr(&det_bad[i / K], 1);
-    }
+    sweep_finite<NT>(kpts, n, K, tid, det_bad);
     __syncthreads();
 
     // ---- 3: the slot of every pose ----
-    if (tid < n) {
-      const int id = det_id[tid];
-      int slot = -1;
-      if (det_ok[tid] != 0 && det_bad[tid] == 0 && id >= 1) {
-        bool first = true;
-        for (int p = 0; p < tid; ++p) first = first && !(det_id[p] == id && det_ok[p] != 0 && det_bad[p] == 0);
-        if (first) {
-          slot = NEEDS_BIRTH;
-          for (int t = S - 1; t >= 0; --t) slot = slot_id[t] == id ? t : slot;   // (the lowest, were there two)
-        }
-      }
-      det_slot[tid] = slot;
-    }
+    if (tid < n) det_slot[tid] = find_slot(det_id, det_ok, det_bad, slot_id, tid, S);
     __syncthreads();
-    if (tid == 0) {   // births, in ascending pose index into the lowest free slot
-      int free_t = 0, dropped = cam_state[1];
-      for (int d = 0; d < n; ++d) {
-        if (det_slot[d] != NEEDS_BIRTH) continue;
-        while (free_t < S && slot_id[free_t] != 0) ++free_t;
-        if (free_t < S) {
-          slot_id[free_t] = det_id[d];
-          g_id[free_t] = det_id[d];
-          det_slot[d] = free_t;
-          det_born[d] = 1;
-        } else {
-          det_slot[d] = -1;
-          dropped = (int)((unsigned)dropped + 1u);
-        }
-      }
-      cam_state[0] = frame;
-      cam_state[1] = dropped;
-      plan.frame[cam] = frame;
-      plan.dropped[cam] = dropped;
-    }
+    if (tid == 0)   // births, in ascending pose index into the lowest free slot; the clock
+      commit_births(plan, cam, n, S, frame, true, g_id, slot_id, det_id, det_slot, det_born, cam_state);
     __syncthreads();
 
     // ---- 4, 5: pose tid in its slot: anchor, cell, splat ----
@@ -191,23 +133,8 @@ __global__ __launch_bounds__(NT) void heat_update_kernel(const pave_heat_plan pl
     if (tid < n) {
       const int t = det_slot[tid];   // (in 0 .. S - 1 or -1: a slot index is a loop counter of step 3)
       if (t >= 0) {
-        long long ax = (long long)X1 + X2, ay = 2ll * Y2;   // the bottom centre of the box
-        if (plan.anchor == PAVE_ZONE_ANCHOR_CENTRE) ay = (long long)Y1 + Y2;
-        if (plan.anchor == PAVE_ZONE_ANCHOR_FEET) {
-          long long sum_x = 0, sum_y = 0, seen = 0;
-          for (int i = 0; i < plan.n_anchor; ++i) {
-            const float* kp = kpts + 3 * (tid * K + plan.anchor_kpt[i]);
-            if (kp[2] > plan.kpt_thr) {
-              sum_x += quant(kp[0], sx);
-              sum_y += quant(kp[1], sy);
-              ++seen;
-            }
-          }
-          if (seen > 0) {   // (sums >= 0: / is floor)
-            ax = 2 * sum_x / seen;
-            ay = 2 * sum_y / seen;
-          }
-        }
+        long long ax, ay;
+        anchor(plan, kpts, tid, K, sx, sy, X1, Y1, X2, Y2, ax, ay);
         if (ax >= 0 && ay >= 0 && ax < 8ll * plan.width && ay < 8ll * plan.height) {
           const int gx = (int)(ax >> (3 + lc)), gy = (int)(ay >> (3 + lc));   // < Gw, < Gh by the test above
           my_cell = gy * Gw + gx;

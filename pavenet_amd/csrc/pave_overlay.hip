@@ -33,11 +33,13 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
 
+using pave_tracked::QMAX;
+
 constexpr int TILE = 32;        // pixels per tile edge
-constexpr int QMAX = 32767;     // the largest quarter-pixel coordinate
 constexpr int MAXZ = PAVE_ZONE_MAX_ZONES;
 constexpr int MAXL = PAVE_ZONE_MAX_LINES;
 constexpr int MAXV = PAVE_ZONE_MAX_VERTICES;

@@ -3,11 +3,10 @@
 // down, hands that go up or down -- on the device, in one launch for up to 32 frames of any number of cameras
 // (pave_posture_events).
 //
-// The rule is DESIGN section 20 and is integer-exact.  A coordinate becomes quarter pixels as in sections 13, 14, 16,
-//   X = clamp((int)rintf((x / sx) * 4.f), 0, 32767)     (correctly rounded division, no contraction),
-// and everything after that is in 1/8 pixel: the centre of a part (shoulders, hips, ankles, wrists; at most 4 key
-// points each) is floor(2 sum X / n) over its n visible key points, as the zones' anchor.  With (dx, dy) = hips -
-// shoulders and all products in int64 the raw class of a frame is
+// The rule is DESIGN section 20 and is integer-exact.  Quarter pixels X, who takes part and the slots are
+// pave_tracked.h's; everything after that is in 1/8 pixel: the centre of a part (shoulders, hips, ankles, wrists; at
+// most 4 key points each) is floor(2 sum X / n) over its n visible key points, as the zones' anchor.  With (dx, dy) =
+// hips - shoulders and all products in int64 the raw class of a frame is
 //   UNKNOWN   no shoulder or no hip visible, or dx = dy = 0
 //   LYING     16 |dy| <= flat |dx|                                  (tested first)
 //   UPRIGHT   dy > 0 and 16 |dx| <= lean dy;  LOW instead iff squat > 0, an ankle is visible and
@@ -17,23 +16,23 @@
 // 16 (shoulders.y - 2 Y) >= hand_up dy.
 // A camera keeps S slots of (id, last, posture, since, upright, streak, alerted, hands, hand_streak), a clock, a drop
 // count and 8 counters.  Per frame: the clock advances; a slot not seen for more than max_age frames is freed; poses
-// find or take slots exactly as in pave_zones.hip; a born slot takes the raw class and the raw hand bit without an
-// event; a slot that was there follows the raw class once it has disagreed with the posture min_frames frames in a
-// row (POSTURE, and FALL when the new posture is LYING within fall_window frames of the last UPRIGHT one), reports
-// DOWN once per stay when frame - since >= down_frames, and debounces "any hand raised" the same way (HANDS_UP /
-// HANDS_DOWN).  A raw UNKNOWN changes neither streak.  Events are rows (kind, index, id, pose, frame), per pose in
-// ascending index POSTURE, FALL, DOWN, then the hands event.
+// find or take slots; a born slot takes the raw class and the raw hand bit without an event; a slot that was there
+// follows the raw class once it has disagreed with the posture min_frames frames in a row (POSTURE, and FALL when the
+// new posture is LYING within fall_window frames of the last UPRIGHT one), reports DOWN once per stay when frame -
+// since >= down_frames, and debounces "any hand raised" the same way (HANDS_UP / HANDS_DOWN).  A raw UNKNOWN changes
+// neither streak.  Events are rows (kind, index, id, pose, frame), per pose in ascending index POSTURE, FALL, DOWN,
+// then the hands event.
 //
-// One block of 128 threads per camera of the launch: block b works iff entry b is the first entry of its camera, and
-// then takes that camera's entries in plan order (frame f + 1 reads the state frame f stored, through the same
-// block), as zone_events_kernel does.  Per frame thread t < S expires slot t, thread d < N classes pose d, finds its
-// slot, and after the serial births of one lane (skipped, by a block-wide vote, in a frame without a birth) does the
-// whole of pose d: at most 16 key points, the class, the slot's stores and the pose's outputs.  What a thread found
-// stays in a bit mask, so its event count is a popcount; an exclusive scan of the 128 counts in LDS gives every
-// thread the row of its first event, whatever order the threads run in.  What a thread's slot and pose add to the 8
-// counters it adds to 8 words in LDS (integer adds: any order gives the same sum), and threads 0 .. 7 carry them to
-// the camera's counters.  Every loop bound is from the plan or the maxima of the header, part counts and indices are
-// clamped as they are read, every barrier is block-uniform, there are no global atomics and no scratch area.
+// One block of 128 threads per camera of the launch (pave_tracked.h).  Its own (DESIGN section 20 has the
+// measurements): thread d tests the finiteness of pose d's key points itself, eight at a time, where the other kernels
+// sweep them with the whole block, and a block-wide vote skips the birth scan in a frame without a birth (the clock
+// and the drop count are stored all the same).  After the births thread d does the whole of pose d: at most 16 key
+// points, the class, the slot's stores and the pose's outputs.  What a thread found stays in a bit mask, so its event
+// count is a popcount; an exclusive scan of the 128 counts in LDS gives every thread the row of its first event,
+// whatever order the threads run in.  What a thread's slot and pose add to the 8 counters it adds to 8 words in LDS
+// (integer adds: any order gives the same sum), and threads 0 .. 7 carry them to the camera's counters.  Every loop
+// bound is from the plan or the maxima of the header, part counts and indices are clamped as they are read, every
+// barrier is block-uniform, there are no global atomics and no scratch area.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -41,8 +40,11 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using namespace pave_tracked;
 
 constexpr int NT = 128;                              // threads of a block
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
@@ -50,19 +52,9 @@ constexpr int MAXS = PAVE_TRACK_MAX_TRACKS;
 constexpr int NPART = PAVE_POSTURE_PARTS;
 constexpr int MAXK = PAVE_POSTURE_MAX_PART;
 constexpr int EW = PAVE_POSTURE_EVENT_WORDS;
-constexpr int QMAX = 32767;                          // the largest quarter-pixel coordinate
-constexpr int NEEDS_BIRTH = -2;
 constexpr int M_POSTURE = 1, M_FALL = 2, M_DOWN = 4, M_HANDS_UP = 8, M_HANDS_DOWN = 16;   // the event bits of a pose
 static_assert(MAXP == NT && MAXS == NT, "one scan item, one pose and one slot per thread");
 static_assert(PAVE_POSTURE_COUNTER_WORDS <= NT && PAVE_POSTURE_CNT_NOW == 0, "thread roles");
-
-// A coordinate in quarter pixels: pave_track.hip's expression (the clamp in float is defined for an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 __device__ __forceinline__ long long absll(const long long v) { return v < 0 ? -v : v; }
 
@@ -92,8 +84,7 @@ __global__ __launch_bounds__(NT) void posture_events_kernel(const pave_posture_p
 
   const int b = blockIdx.x;
   const int cam = plan.camera[b];
-  for (int e = 0; e < b; ++e)
-    if (plan.camera[e] == cam) return;   // (block-uniform, before any barrier: an earlier block has this camera)
+  if (!owns_camera(plan, b, cam)) return;   // (block-uniform, before any barrier: an earlier block has this camera)
   const int tid = threadIdx.x;
   const int S = plan.S, K = plan.K;
   int32_t* __restrict__ g_id = plan.slot_id + (long long)cam * S;
@@ -127,24 +118,15 @@ __global__ __launch_bounds__(NT) void posture_events_kernel(const pave_posture_p
 
     // ---- 1, 2: expire the slots; the poses' boxes ----
     int gone = -1, gone_hand = 0;   // the posture and the hand bit of slot tid if it expires in this frame
-    {
-      int id = 0;
-      if (tid < S) {
-        id = g_id[tid];
-        if (id != 0 && (long long)frame - g_last[tid] > plan.max_age) {
-          gone = g_posture[tid];
-          gone_hand = g_hands[tid] != 0 ? 1 : 0;
-          id = 0;
-          g_id[tid] = 0;
-        }
-      }
-      slot_id[tid] = id;
-      if (tid < PAVE_POSTURE_COUNTER_WORDS) count_delta[tid] = 0;
+    if (expire_slot(plan, g_id, g_last, slot_id, tid, S, frame) != 0) {
+      gone = g_posture[tid];
+      gone_hand = g_hands[tid] != 0 ? 1 : 0;
     }
+    if (tid < PAVE_POSTURE_COUNTER_WORDS) count_delta[tid] = 0;
     if (tid < n) {
-      const float* bb = bboxes + tid * 5;
-      const float b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
-      int bad = isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3) ? 0 : 1;
+      int X1, Y1, X2, Y2;   // (unused: a posture is made of key points)
+      int bad = classify_pose(bboxes, keep, ids, sx, sy, plan.score_thr, tid, det_id, det_bad, det_ok, det_born, X1, Y1,
+                              X2, Y2);
       const float* kp = kpts + 3 * (tid * K);
       for (int k0 = 0; k0 < K; k0 += 8) {   // eight key points at a time: sixteen loads that do not wait for each other
 #pragma unroll
@@ -155,47 +137,15 @@ __global__ __launch_bounds__(NT) void posture_events_kernel(const pave_posture_p
         }
       }
       det_bad[tid] = bad;
-      det_ok[tid] = (keep == nullptr || keep[tid] != 0) && bb[4] > plan.score_thr ? 1 : 0;
-      det_id[tid] = ids[tid];
-      det_born[tid] = 0;
     }
     __syncthreads();
 
     // ---- 2: the slot of every pose ----
     int slot = -1;
-    if (tid < n) {
-      const int id = det_id[tid];
-      if (det_ok[tid] != 0 && det_bad[tid] == 0 && id >= 1) {
-        bool first = true;
-        for (int p = 0; p < tid; ++p) first = first && !(det_id[p] == id && det_ok[p] != 0 && det_bad[p] == 0);
-        if (first) {
-          slot = NEEDS_BIRTH;
-          for (int t = S - 1; t >= 0; --t) slot = slot_id[t] == id ? t : slot;   // (the lowest, were there two)
-        }
-      }
-      det_slot[tid] = slot;
-    }
+    if (tid < n) det_slot[tid] = slot = find_slot(det_id, det_ok, det_bad, slot_id, tid, S);
     const int births = __syncthreads_or(slot == NEEDS_BIRTH ? 1 : 0);   // (block-uniform: every thread votes)
-    if (tid == 0) {   // births, in ascending pose index into the lowest free slot
-      int free_t = 0, dropped = cam_state[1];
-      for (int d = 0; births != 0 && d < n; ++d) {
-        if (det_slot[d] != NEEDS_BIRTH) continue;
-        while (free_t < S && slot_id[free_t] != 0) ++free_t;
-        if (free_t < S) {
-          slot_id[free_t] = det_id[d];
-          g_id[free_t] = det_id[d];
-          det_slot[d] = free_t;
-          det_born[d] = 1;
-        } else {
-          det_slot[d] = -1;
-          dropped = (int)((unsigned)dropped + 1u);
-        }
-      }
-      cam_state[0] = frame;
-      cam_state[1] = dropped;
-      plan.frame[cam] = frame;
-      plan.dropped[cam] = dropped;
-    }
+    if (tid == 0)   // births, in ascending pose index into the lowest free slot; the clock, whatever was born
+      commit_births(plan, cam, n, S, frame, births != 0, g_id, slot_id, det_id, det_slot, det_born, cam_state);
     __syncthreads();
 
     // ---- 3 .. 7: pose tid in its slot ----

@@ -37,25 +37,21 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using pave_tracked::QMAX;
+using pave_tracked::quant;
 
 constexpr int NT = 256;
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
 constexpr int MAXS = PAVE_TRACK_MAX_TRACKS;
 constexpr int BINS = PAVE_REID_BINS;
-constexpr int QMAX = 32767;
 constexpr int MAX_SIZE = 8192;
 constexpr int PAIRS_PER_THREAD = MAXP * MAXS / NT;   // of the greedy choice
 static_assert(BINS == NT, "one bin per thread");
 static_assert(MAXP <= 128 && MAXS <= 128 && 2 * MAXP <= NT, "thread roles and the 7-bit fields of the greedy key");
-
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 // keep, a box score above the threshold and finite coordinates; B: the quantised box
 __device__ bool pose_usable(const pave_reid_describe_plan& plan, const int e, const int d, int (&B)[4]) {

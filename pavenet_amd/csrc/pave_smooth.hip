@@ -1,15 +1,12 @@
 // Steady poses for the live path: a per-track adaptive exponential filter on the key points and the box corners of
 // tracked poses, on the device, in one launch for up to 32 frames of any number of cameras (pave_smooth_poses).
 //
-// The rule is DESIGN section 16 and is integer-exact.  A coordinate becomes quarter pixels as in sections 13 and 14,
-//   X = clamp((int)rintf((x / sx) * 4.f), 0, 32767)     (correctly rounded division, no contraction),
-// and a state position is Z = 16 X, 1/64 pixel.  A pose has J = K + 2 points: its key points (visible iff their
-// score is > kpt_thr), then its box corners (always visible).  A camera keeps S slots of (id, last, pos [J, 2],
-// vel [J, 2]); a point with pos x < 0 is uninitialised.  Per frame: the clock advances and old slots expire; a pose
-// is unusable iff a coordinate is not finite, valid by section 14's rule, and filtered iff it is valid, its id is
-// >= 1, no valid pose before it has the same id and it has a slot -- the live slot of its id, or, born in ascending
-// pose index, the lowest free one (none: dropped + 1).  A point of a filtered pose in a slot that was there before,
-// visible and initialised, per axis in int64 with gap = frame - last and g = velocity_gain:
+// The rule is DESIGN section 16 and is integer-exact.  Quarter pixels X, the slots and who is filtered (who "takes
+// part") are pave_tracked.h's; a state position is Z = 16 X, 1/64 pixel.  A pose has J = K + 2 points: its key points
+// (visible iff their score is > kpt_thr), then its box corners (always visible).  A slot holds (id, last, pos [J, 2],
+// vel [J, 2]); a point with pos x < 0 is uninitialised; a pose is unusable iff a coordinate is not finite.  A point of
+// a filtered pose in a slot that was there before, visible and initialised, per axis in int64 with gap = frame - last
+// and g = velocity_gain:
 //   e = Z - pos;   r = floor((2 e + gap) / (2 gap));   vel = (g r + (16 - g) vel + 8) >> 4
 // then with s = max(|X2 - X1|, |Y2 - Y1|, 1) of the pose's box
 //   u = ((|vel_x| + |vel_y|) << 6) / s;   alpha = min(256, alpha_min + ((beta u) >> 4))
@@ -18,13 +15,11 @@
 // Out goes pos / 64 of a filtered pose (Z / 64 where the point is not initialised), Z / 64 of any other usable pose,
 // the quiet NaN of an unusable one, and the scores as they came.
 //
-// One block of 256 threads per camera of the launch: block b works iff entry b is the first entry of its camera, and
-// then takes that camera's entries in plan order (frame f + 1 reads the state frame f stored, through the same
-// block), as track_poses_kernel does.  No two blocks touch one camera's state.  Per frame: slot ids and pose ids go
-// into LDS, thread d finds the slot and the duplicates of pose d by two scans of at most 128 words, births are a
-// serial scan by one lane, and the N J points are spread over the block: each reads its pos / vel pair from global
-// memory, filters it and stores it.  No two poses of a frame share a slot, so no two threads share a point.  Every
-// loop bound is from the plan, every barrier is block-uniform, there are no global atomics and no scratch area.
+// One block of 256 threads per camera of the launch (pave_tracked.h).  Its own: slot_last is kept in LDS as the frame
+// before left it, since the gap is read after `last` is stored, and det_size is s of the pose's box.  After the births
+// the N J points are spread over the block: each reads its pos / vel pair from global memory, filters it and stores
+// it.  No two poses of a frame share a slot, so no two threads share a point.  Every loop bound is from the plan,
+// every barrier is block-uniform, there are no global atomics and no scratch area.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -32,30 +27,17 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using namespace pave_tracked;
 
 constexpr int NT = 256;                              // threads of a block
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
 constexpr int MAXS = PAVE_TRACK_MAX_TRACKS;
-constexpr int QMAX = 32767;                          // the largest quarter-pixel coordinate
 constexpr long long PMAX = 16 * QMAX;                // the largest state position
 constexpr unsigned int QUIET_NAN = 0x7fc00000u;
-constexpr int NEEDS_BIRTH = -2;
-
-// A coordinate in quarter pixels: pave_track.hip's expression (the clamp in float is defined for an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
-
-// floor(a / b) for b > 0 (C's / truncates)
-__device__ __forceinline__ long long floor_div(const long long a, const long long b) {
-  const long long q = a / b;
-  return q - ((a % b) < 0 ? 1 : 0);
-}
 
 __device__ __forceinline__ long long abs64(const long long v) { return v < 0 ? -v : v; }
 
@@ -72,8 +54,7 @@ __global__ __launch_bounds__(NT) void smooth_poses_kernel(const pave_smooth_plan
 
   const int b = blockIdx.x;
   const int cam = plan.camera[b];
-  for (int e = 0; e < b; ++e)
-    if (plan.camera[e] == cam) return;   // (block-uniform, before any barrier: an earlier block has this camera)
+  if (!owns_camera(plan, b, cam)) return;   // (block-uniform, before any barrier: an earlier block has this camera)
   const int tid = threadIdx.x;
   const int S = plan.S, K = plan.K, J = K + 2;
   int32_t* __restrict__ g_id = plan.slot_id + (long long)cam * S;
@@ -102,67 +83,24 @@ __global__ __launch_bounds__(NT) void smooth_poses_kernel(const pave_smooth_plan
 
     // ---- 1, 2: expire the slots; the poses' boxes ----
     if (tid < S) {
-      int id = g_id[tid];
-      const int last = g_last[tid];
-      if (id != 0 && (long long)frame - last > plan.max_age) {
-        id = 0;
-        g_id[tid] = 0;
-      }
-      slot_id[tid] = id;
+      const int last = g_last[tid];   // (read beside the id, not behind it: expire_slot's own read folds into this one)
+      expire_slot(plan, g_id, g_last, slot_id, tid, S, frame);
       slot_last[tid] = last;
     }
     if (tid < n) {
-      const float* bb = bboxes + tid * 5;
-      const float b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
-      const int X1 = quant(b0, sx), Y1 = quant(b1, sy), X2 = quant(b2, sx), Y2 = quant(b3, sy);
-      det_bad[tid] = isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3) ? 0 : 1;
-      det_ok[tid] = (keep == nullptr || keep[tid] != 0) && bb[4] > plan.score_thr ? 1 : 0;
+      int X1, Y1, X2, Y2;
+      classify_pose(bboxes, keep, ids, sx, sy, plan.score_thr, tid, det_id, det_bad, det_ok, det_born, X1, Y1, X2, Y2);
       det_size[tid] = max(max(abs(X2 - X1), abs(Y2 - Y1)), 1);
-      det_id[tid] = ids[tid];
-      det_born[tid] = 0;
     }
     __syncthreads();
-    for (int i = tid; i < n * K; i += NT) {
-      const float x = kpts[3 * i], y = kpts[3 * i + 1];
-      if (!(isfinite(x) && isfinite(y))) atomicOr(&det_bad[i / K], 1);
-    }
+    sweep_finite<NT>(kpts, n, K, tid, det_bad);
     __syncthreads();
 
     // ---- 3: the slot of every pose ----
-    if (tid < n) {
-      const int id = det_id[tid];
-      int slot = -1;
-      if (det_ok[tid] != 0 && det_bad[tid] == 0 && id >= 1) {
-        bool first = true;
-        for (int p = 0; p < tid; ++p) first = first && !(det_id[p] == id && det_ok[p] != 0 && det_bad[p] == 0);
-        if (first) {
-          slot = NEEDS_BIRTH;
-          for (int t = S - 1; t >= 0; --t) slot = slot_id[t] == id ? t : slot;   // (the lowest, were there two)
-        }
-      }
-      det_slot[tid] = slot;
-    }
+    if (tid < n) det_slot[tid] = find_slot(det_id, det_ok, det_bad, slot_id, tid, S);
     __syncthreads();
-    if (tid == 0) {   // births, in ascending pose index into the lowest free slot
-      int free_t = 0, dropped = cam_state[1];
-      for (int d = 0; d < n; ++d) {
-        if (det_slot[d] != NEEDS_BIRTH) continue;
-        while (free_t < S && slot_id[free_t] != 0) ++free_t;
-        if (free_t < S) {
-          slot_id[free_t] = det_id[d];
-          g_id[free_t] = det_id[d];
-          det_slot[d] = free_t;
-          det_born[d] = 1;
-        } else {
-          det_slot[d] = -1;
-          dropped = (int)((unsigned)dropped + 1u);
-        }
-      }
-      cam_state[0] = frame;
-      cam_state[1] = dropped;
-      plan.frame[cam] = frame;
-      plan.dropped[cam] = dropped;
-    }
+    if (tid == 0)   // births, in ascending pose index into the lowest free slot; the clock
+      commit_births(plan, cam, n, S, frame, true, g_id, slot_id, det_id, det_slot, det_born, cam_state);
     __syncthreads();
 
     // ---- 4, 5, 6: the points ----

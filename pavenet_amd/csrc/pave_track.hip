@@ -34,26 +34,22 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using pave_tracked::QMAX;
+using pave_tracked::quant;
+using pave_tracked::floor_div;
 
 constexpr int NT = 256;                              // threads of a block
 constexpr int WAVES = NT / 64;
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
 constexpr int MAXT = PAVE_TRACK_MAX_TRACKS;
 constexpr int ROW = PAVE_TRACK_MAX_K + 1;            // words of a row of packed points (odd: no bank conflicts)
-constexpr int QMAX = 32767;                          // the largest quarter-pixel coordinate
 constexpr long long DMAX = (1ll << 37) - 1;
 
 typedef unsigned long long u64;
-
-// A coordinate in quarter pixels: pave_draw.hip's expression (the clamp in float is defined for an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 __device__ __forceinline__ u64 wave_max(u64 v) {
 #pragma unroll
@@ -62,12 +58,6 @@ __device__ __forceinline__ u64 wave_max(u64 v) {
     v = w > v ? w : v;
   }
   return v;
-}
-
-// floor(a / b) for b > 0 (C's / truncates)
-__device__ __forceinline__ long long floor_div(const long long a, const long long b) {
-  const long long q = a / b;
-  return q - ((a % b) < 0 ? 1 : 0);
 }
 
 template <bool MOTION>

@@ -4,7 +4,7 @@
 // 3] BGR).
 //
 // Both rules are DESIGN section 22 and are integer-exact.
-//   update: section 17's poses, slots and 1/8-pixel anchor, unchanged.  Per frame: the clock advances and slots not
+//   update: section 17's poses, slots and 1/8-pixel anchor (pave_tracked.h).  Per frame: the clock advances and slots not
 //     seen for more than max_age frames are freed; poses find or take slots; a birth starts the ring with the anchor
 //     (head 0, count 1); a slot that was there takes the anchor as pos and, when the newest committed point is at
 //     least `stride` frames old and at least min_step away (Chebyshev), commits it: head = (head + 1) % L, count =
@@ -16,8 +16,8 @@
 //     n), and (head_radius > 0) disc j = n lies at pos; pave_draw.hip's coverage rule; a pixel takes the colour of the
 //     covering primitive with the largest (id, j), an NV12 chroma sample the largest over its 2 x 2 luma pixels.
 //
-// Update: pave_zones.hip's scheme, one block of 256 threads per camera of the launch, which takes that camera's entries
-// in plan order with a block barrier between them; launches on one stream follow each other.  A slot has at most one
+// Update: one block of 256 threads per camera of the launch (pave_tracked.h), which takes that camera's entries in
+// plan order with a block barrier between them; launches on one stream follow each other.  A slot has at most one
 // pose per frame (the first valid pose of its id), so its ring has one writer.  head and count live in device memory:
 // wherever they index the ring they are first reduced, (unsigned)head % L and count clamped to 1 .. L, and the walk
 // over the ring is bounded by that count: no bit pattern in the state can make an access leave the ring.
@@ -37,25 +37,18 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using namespace pave_tracked;
 
 constexpr int NT = 256;                              // threads of a block
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
 constexpr int MAXS = PAVE_TRACK_MAX_TRACKS;
 constexpr int MAXL = PAVE_TRAIL_MAX_POINTS;
-constexpr int QMAX = 32767;                          // the largest quarter-pixel coordinate
-constexpr int NEEDS_BIRTH = -2;
 constexpr int TILE = 32;                             // pixels per tile edge of the draw kernels
 static_assert(MAXP <= NT && MAXS <= NT && MAXL < 128, "thread roles; the key (id, j) as id * 128 + j");
-
-// A coordinate in quarter pixels: pave_track.hip's expression (the clamp in float is defined for an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 // floor(sqrt(dx^2 + dy^2)).  The rule's own operands are below 2^34, where the double square root is exact enough
 // for its floor to be right; the two corrections make the result the floor whatever the rounding, and the unsigned
@@ -80,8 +73,7 @@ __global__ __launch_bounds__(NT) void trail_update_kernel(const pave_trail_plan 
 
   const int b = blockIdx.x;
   const int cam = plan.camera[b];
-  for (int e = 0; e < b; ++e)
-    if (plan.camera[e] == cam) return;   // (block-uniform, before any barrier: an earlier block has this camera)
+  if (!owns_camera(plan, b, cam)) return;   // (block-uniform, before any barrier: an earlier block has this camera)
   const int tid = threadIdx.x;
   const int S = plan.S, K = plan.K, L = plan.L;
   int32_t* __restrict__ g_id = plan.slot_id + (long long)cam * S;
@@ -110,69 +102,19 @@ __global__ __launch_bounds__(NT) void trail_update_kernel(const pave_trail_plan 
     const int frame = (int)((unsigned)cam_state[0] + 1u);
 
     // ---- 1: expire the slots; the poses' boxes ----
-    if (tid < MAXS) {
-      int id = 0;
-      if (tid < S) {
-        id = g_id[tid];
-        if (id != 0 && (long long)frame - g_last[tid] > plan.max_age) {
-          id = 0;
-          g_id[tid] = 0;
-        }
-      }
-      slot_id[tid] = id;
-    }
+    if (tid < MAXS) expire_slot(plan, g_id, g_last, slot_id, tid, S, frame);
     int X1 = 0, Y1 = 0, X2 = 0, Y2 = 0;
-    if (tid < n) {
-      const float* bb = bboxes + tid * 5;
-      const float b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
-      X1 = quant(b0, sx), Y1 = quant(b1, sy), X2 = quant(b2, sx), Y2 = quant(b3, sy);
-      det_bad[tid] = isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3) ? 0 : 1;
-      det_ok[tid] = (keep == nullptr || keep[tid] != 0) && bb[4] > plan.score_thr ? 1 : 0;
-      det_id[tid] = ids[tid];
-      det_born[tid] = 0;
-    }
+    if (tid < n)
+      classify_pose(bboxes, keep, ids, sx, sy, plan.score_thr, tid, det_id, det_bad, det_ok, det_born, X1, Y1, X2, Y2);
     __syncthreads();
-    for (int i = tid; i < n * K; i += NT) {
-      const float x = kpts[3 * i], y = kpts[3 * i + 1];
-      if (!(isfinite(x) && isfinite(y))) atomicOr(&det_bad[i / K], 1);
-    }
+    sweep_finite<NT>(kpts, n, K, tid, det_bad);
     __syncthreads();
 
     // ---- 2: the slot of every pose ----
-    if (tid < n) {
-      const int id = det_id[tid];
-      int slot = -1;
-      if (det_ok[tid] != 0 && det_bad[tid] == 0 && id >= 1) {
-        bool first = true;
-        for (int p = 0; p < tid; ++p) first = first && !(det_id[p] == id && det_ok[p] != 0 && det_bad[p] == 0);
-        if (first) {
-          slot = NEEDS_BIRTH;
-          for (int t = S - 1; t >= 0; --t) slot = slot_id[t] == id ? t : slot;   // (the lowest, were there two)
-        }
-      }
-      det_slot[tid] = slot;
-    }
+    if (tid < n) det_slot[tid] = find_slot(det_id, det_ok, det_bad, slot_id, tid, S);
     __syncthreads();
-    if (tid == 0) {   // births, in ascending pose index into the lowest free slot
-      int free_t = 0, dropped = cam_state[1];
-      for (int d = 0; d < n; ++d) {
-        if (det_slot[d] != NEEDS_BIRTH) continue;
-        while (free_t < S && slot_id[free_t] != 0) ++free_t;
-        if (free_t < S) {
-          slot_id[free_t] = det_id[d];
-          g_id[free_t] = det_id[d];
-          det_slot[d] = free_t;
-          det_born[d] = 1;
-        } else {
-          det_slot[d] = -1;
-          dropped = (int)((unsigned)dropped + 1u);
-        }
-      }
-      cam_state[0] = frame;
-      cam_state[1] = dropped;
-      plan.frame[cam] = frame;
-      plan.dropped[cam] = dropped;
-    }
+    if (tid == 0)   // births, in ascending pose index into the lowest free slot; the clock
+      commit_births(plan, cam, n, S, frame, true, g_id, slot_id, det_id, det_slot, det_born, cam_state);
     __syncthreads();
 
     // ---- 3, 4, 5: pose tid in its slot: anchor, commit, box, outputs ----
@@ -180,23 +122,8 @@ __global__ __launch_bounds__(NT) void trail_update_kernel(const pave_trail_plan 
       int o_count = 0, o_span = 0, o_dist = 0, o_path = 0;
       const int t = det_slot[tid];   // (in 0 .. S - 1 or -1: a slot index is a loop counter of step 2)
       if (t >= 0) {
-        long long lx = (long long)X1 + X2, ly = 2ll * Y2;   // the bottom centre of the box
-        if (plan.anchor == PAVE_ZONE_ANCHOR_CENTRE) ly = (long long)Y1 + Y2;
-        if (plan.anchor == PAVE_ZONE_ANCHOR_FEET) {
-          long long sum_x = 0, sum_y = 0, seen = 0;
-          for (int i = 0; i < plan.n_anchor; ++i) {
-            const float* kp = kpts + 3 * (tid * K + plan.anchor_kpt[i]);
-            if (kp[2] > plan.kpt_thr) {
-              sum_x += quant(kp[0], sx);
-              sum_y += quant(kp[1], sy);
-              ++seen;
-            }
-          }
-          if (seen > 0) {   // (sums >= 0: / is floor)
-            lx = 2 * sum_x / seen;
-            ly = 2 * sum_y / seen;
-          }
-        }
+        long long lx, ly;
+        anchor(plan, kpts, tid, K, sx, sy, X1, Y1, X2, Y2, lx, ly);
         const int ax = (int)lx, ay = (int)ly;   // (0 .. 65534)
         int32_t* ring = g_pts + (long long)t * L * 2;
         int32_t* ring_when = g_when + (long long)t * L;

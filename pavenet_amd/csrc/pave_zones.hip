@@ -2,34 +2,29 @@
 // directed line a track crossed, on the device, in one launch for up to 32 frames of any number of cameras
 // (pave_zone_events).
 //
-// The rule is DESIGN section 17 and is integer-exact.  A coordinate becomes quarter pixels as in sections 13, 14, 16,
-//   X = clamp((int)rintf((x / sx) * 4.f), 0, 32767)     (correctly rounded division, no contraction),
-// and everything after that is in 1/8 pixel: the anchor of a pose (floor(2 sum X / n) over its n visible anchor key
-// points, or the bottom centre (X1 + X2, 2 Y2) / the centre (X1 + X2, Y1 + Y2) of its box) and the geometry, at most
-// 8 polygons of at most 16 vertices and 8 directed lines per camera.  All products are int64.
+// The rule is DESIGN section 17 and is integer-exact.  Who takes part, the slots and the anchor of a pose in 1/8
+// pixel are pave_tracked.h's; the geometry is in 1/8 pixel too, at most 8 polygons of at most 16 vertices and 8
+// directed lines per camera.  All products are int64.
 //   inside(P, polygon): even-odd; an edge (a, b) with (a.y > P.y) != (b.y > P.y) toggles iff, with dy = b.y - a.y and
 //     t = (P.x - a.x) dy - (P.y - a.y)(b.x - a.x), dy > 0 ? t < 0 : t > 0
 //   s(P) on A -> B: cross(B - A, P - A) >= 0; a move Q -> P, Q != P, crosses iff s(Q) != s(P) and A and B are on
 //     different sides of Q -> P by the same test; forward iff s(Q) is false
 // A camera keeps S slots of (id, last, pos [2], inside, alerted, streak [8], since [8]), a clock, a drop count and 56
 // counters.  Per frame: the clock advances; a slot not seen for more than max_age frames is freed (VANISH for every
-// zone it was inside); poses find or take slots exactly as in pave_smooth.hip; a born slot takes the raw test as its
-// inside bits (APPEAR); a slot that was there flips bit z once the raw test has disagreed with it min_frames frames
-// in a row (ENTER / EXIT), is reported once per stay when frame - since >= dwell_frames (DWELL), and is tested
-// against every line on its move pos -> anchor (CROSS_FWD / CROSS_BACK).  Events are rows (kind, index, id, pose,
-// frame) in a fixed order: VANISH by slot then zone, then per pose in ascending index its zones (flip or APPEAR, then
-// DWELL), then its lines.
+// zone it was inside); poses find or take slots; a born slot takes the raw test as its inside bits (APPEAR); a slot
+// that was there flips bit z once the raw test has disagreed with it min_frames frames in a row (ENTER / EXIT), is
+// reported once per stay when frame - since >= dwell_frames (DWELL), and is tested against every line on its move pos
+// -> anchor (CROSS_FWD / CROSS_BACK).  Events are rows (kind, index, id, pose, frame) in a fixed order: VANISH by slot
+// then zone, then per pose in ascending index its zones (flip or APPEAR, then DWELL), then its lines.
 //
-// One block of 256 threads per camera of the launch: block b works iff entry b is the first entry of its camera, and
-// then takes that camera's entries in plan order (frame f + 1 reads the state frame f stored, through the same
-// block), as smooth_poses_kernel does.  The camera's geometry goes into LDS once.  Per frame thread t < S expires
-// slot t, thread d < N classes pose d, finds its slot, and after the serial births of one lane does the whole of
-// pose d: anchor, at most 128 edge tests, 8 line tests, the slot's stores and the pose's outputs.  What a thread
+// One block of 256 threads per camera of the launch (pave_tracked.h).  The camera's geometry goes into LDS once.  Per
+// frame thread t < S expires slot t, thread d < N classes pose d, finds its slot, and after the births does the whole
+// of pose d: anchor, at most 128 edge tests, 8 line tests, the slot's stores and the pose's outputs.  What a thread
 // found stays in bit masks, so its event count is a popcount; an exclusive scan of the 256 counts (the slots', then
-// the poses') in LDS gives every thread the row of its first event, whatever order the threads run in.  Threads 128
-// .. 183 add the masks up into the counters, one counter each.  Every loop bound is from the plan or the maxima of
-// the header, geometry counts are clamped as they are read, every barrier is block-uniform, there are no global
-// atomics and no scratch area.
+// the poses') in LDS gives every thread the row of its first event, whatever order the threads run in.  Threads 128 ..
+// 183 add the masks up into the counters, one counter each.  Every loop bound is from the plan or the maxima of the
+// header, geometry counts are clamped as they are read, every barrier is block-uniform, there are no global atomics
+// and no scratch area.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -37,8 +32,11 @@
 
 #include "pave_hip.h"
 #include "pave_internal.h"
+#include "pave_tracked.h"
 
 namespace {
+
+using namespace pave_tracked;
 
 constexpr int NT = 256;                              // threads of a block
 constexpr int MAXP = PAVE_TRACK_MAX_POSES;
@@ -47,18 +45,8 @@ constexpr int MAXZ = PAVE_ZONE_MAX_ZONES;
 constexpr int MAXL = PAVE_ZONE_MAX_LINES;
 constexpr int MAXV = PAVE_ZONE_MAX_VERTICES;
 constexpr int EW = PAVE_ZONE_EVENT_WORDS;
-constexpr int QMAX = 32767;                          // the largest quarter-pixel coordinate
-constexpr int NEEDS_BIRTH = -2;
 static_assert(MAXP + MAXS == NT, "one scan item per thread: the slots, then the poses");
 static_assert(MAXP <= 128 && MAXS <= 128 && PAVE_ZONE_COUNTER_WORDS <= NT - 128, "thread roles");
-
-// A coordinate in quarter pixels: pave_track.hip's expression (the clamp in float is defined for an infinite quotient).
-__device__ __forceinline__ int quant(const float x, const float s) {
-#pragma clang fp contract(off)
-  const float q = __fdiv_rn(x, s);
-  const float v = q * 4.f;
-  return (int)fminf(fmaxf(rintf(v), 0.f), (float)QMAX);
-}
 
 // cross(u, v) >= 0
 __device__ __forceinline__ bool left_of(const long long ux, const long long uy, const long long vx, const long long vy) {
@@ -94,8 +82,7 @@ __global__ __launch_bounds__(NT) void zone_events_kernel(const pave_zone_plan pl
 
   const int b = blockIdx.x;
   const int cam = plan.camera[b];
-  for (int e = 0; e < b; ++e)
-    if (plan.camera[e] == cam) return;   // (block-uniform, before any barrier: an earlier block has this camera)
+  if (!owns_camera(plan, b, cam)) return;   // (block-uniform, before any barrier: an earlier block has this camera)
   const int tid = threadIdx.x;
   const int S = plan.S, K = plan.K;
   int32_t* __restrict__ g_id = plan.slot_id + (long long)cam * S;
@@ -140,71 +127,22 @@ __global__ __launch_bounds__(NT) void zone_events_kernel(const pave_zone_plan pl
     // ---- 1, 2: expire the slots; the poses' boxes ----
     int vanish = 0, vanish_id = 0;
     if (tid < MAXS) {
-      int id = 0;
-      if (tid < S) {
-        id = g_id[tid];
-        if (id != 0 && (long long)frame - g_last[tid] > plan.max_age) {
-          vanish = g_inside[tid] & zmask;
-          vanish_id = id;
-          id = 0;
-          g_id[tid] = 0;
-        }
-      }
-      slot_id[tid] = id;
+      vanish_id = expire_slot(plan, g_id, g_last, slot_id, tid, S, frame);
+      if (vanish_id != 0) vanish = g_inside[tid] & zmask;
       m_vanish[tid] = vanish;
     }
     int X1 = 0, Y1 = 0, X2 = 0, Y2 = 0;
-    if (tid < n) {
-      const float* bb = bboxes + tid * 5;
-      const float b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
-      X1 = quant(b0, sx), Y1 = quant(b1, sy), X2 = quant(b2, sx), Y2 = quant(b3, sy);
-      det_bad[tid] = isfinite(b0) && isfinite(b1) && isfinite(b2) && isfinite(b3) ? 0 : 1;
-      det_ok[tid] = (keep == nullptr || keep[tid] != 0) && bb[4] > plan.score_thr ? 1 : 0;
-      det_id[tid] = ids[tid];
-      det_born[tid] = 0;
-    }
+    if (tid < n)
+      classify_pose(bboxes, keep, ids, sx, sy, plan.score_thr, tid, det_id, det_bad, det_ok, det_born, X1, Y1, X2, Y2);
     __syncthreads();
-    for (int i = tid; i < n * K; i += NT) {
-      const float x = kpts[3 * i], y = kpts[3 * i + 1];
-      if (!(isfinite(x) && isfinite(y))) atomicOr(&det_bad[i / K], 1);
-    }
+    sweep_finite<NT>(kpts, n, K, tid, det_bad);
     __syncthreads();
 
     // ---- 2: the slot of every pose ----
-    if (tid < n) {
-      const int id = det_id[tid];
-      int slot = -1;
-      if (det_ok[tid] != 0 && det_bad[tid] == 0 && id >= 1) {
-        bool first = true;
-        for (int p = 0; p < tid; ++p) first = first && !(det_id[p] == id && det_ok[p] != 0 && det_bad[p] == 0);
-        if (first) {
-          slot = NEEDS_BIRTH;
-          for (int t = S - 1; t >= 0; --t) slot = slot_id[t] == id ? t : slot;   // (the lowest, were there two)
-        }
-      }
-      det_slot[tid] = slot;
-    }
+    if (tid < n) det_slot[tid] = find_slot(det_id, det_ok, det_bad, slot_id, tid, S);
     __syncthreads();
-    if (tid == 0) {   // births, in ascending pose index into the lowest free slot
-      int free_t = 0, dropped = cam_state[1];
-      for (int d = 0; d < n; ++d) {
-        if (det_slot[d] != NEEDS_BIRTH) continue;
-        while (free_t < S && slot_id[free_t] != 0) ++free_t;
-        if (free_t < S) {
-          slot_id[free_t] = det_id[d];
-          g_id[free_t] = det_id[d];
-          det_slot[d] = free_t;
-          det_born[d] = 1;
-        } else {
-          det_slot[d] = -1;
-          dropped = (int)((unsigned)dropped + 1u);
-        }
-      }
-      cam_state[0] = frame;
-      cam_state[1] = dropped;
-      plan.frame[cam] = frame;
-      plan.dropped[cam] = dropped;
-    }
+    if (tid == 0)   // births, in ascending pose index into the lowest free slot; the clock
+      commit_births(plan, cam, n, S, frame, true, g_id, slot_id, det_id, det_slot, det_born, cam_state);
     __syncthreads();
 
     // ---- 3, 4, 5: pose tid in its slot ----
@@ -215,23 +153,8 @@ __global__ __launch_bounds__(NT) void zone_events_kernel(const pave_zone_plan pl
 #pragma unroll
       for (int z = 0; z < MAXZ; ++z) dwell_of[z] = 0;
       if (t >= 0) {
-        long long ax = (long long)X1 + X2, ay = 2ll * Y2;   // the bottom centre of the box
-        if (plan.anchor == PAVE_ZONE_ANCHOR_CENTRE) ay = (long long)Y1 + Y2;
-        if (plan.anchor == PAVE_ZONE_ANCHOR_FEET) {
-          long long sum_x = 0, sum_y = 0, seen = 0;
-          for (int i = 0; i < plan.n_anchor; ++i) {
-            const float* kp = kpts + 3 * (tid * K + plan.anchor_kpt[i]);
-            if (kp[2] > plan.kpt_thr) {
-              sum_x += quant(kp[0], sx);
-              sum_y += quant(kp[1], sy);
-              ++seen;
-            }
-          }
-          if (seen > 0) {   // (sums >= 0: / is floor)
-            ax = 2 * sum_x / seen;
-            ay = 2 * sum_y / seen;
-          }
-        }
+        long long ax, ay;
+        anchor(plan, kpts, tid, K, sx, sy, X1, Y1, X2, Y2, ax, ay);
         int raw = 0;
         for (int z = 0; z < nz; ++z) {
           const int nv = geom[PAVE_ZONE_GEOM_NVERT + z];

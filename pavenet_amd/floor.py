@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import native, ops
-from .render import _poses, _scales
+from .tracked import Tracked
 from .zones import ANKLES
 
 _STATE = ('id', 'last', 'hits', 'pos', 'vel', 'travel', 'frame', 'dropped')
@@ -129,13 +129,14 @@ def calibrate(points=None, matrix=None, bounds=None, who='GroundPlane.set_plane'
     return H, row
 
 
-class GroundPlane:
+class GroundPlane(Tracked):
     """The floor under `cameras` cameras.  Who takes part, the slots (`max_tracks` 1 .. 128, freed after `max_age`
     frames unseen), `anchor`, `anchor_kpts`, `score_thr` and `kpt_thr` are ``ZoneMonitor``'s, with one condition more:
     the pose's anchor projects onto the floor inside the camera's bounds.  `velocity_gain` (1 .. 16): sixteenths of a
     track's newest move that go into its velocity.  `near` (0 .. 2^20 mm): the radius within which neighbours are
     counted.  `unit` (1 .. 1000 mm) and `origin` ((x, y) in mm): a pixel of the plan that ``out['floor']`` is drawn on
     and the floor point of its corner."""
+    _NOUN, _NOUNS = 'the plane', "the plane's"
 
     def __init__(self, K, cameras=1, max_tracks=128, max_age=30, anchor='feet', anchor_kpts=None, velocity_gain=4,
                  near=1500, unit=10, origin=(0, 0), score_thr=0.3, kpt_thr=0.):
@@ -184,11 +185,6 @@ class GroundPlane:
                            dropped=torch.zeros((C,), **z))
         self._calib = torch.zeros((C, native.FLOOR_CALIB_WORDS), dtype=torch.int64, device=dev)
 
-    def _camera(self, camera, who):
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < self.cameras:
-            raise ValueError(f'{who}: camera must be an integer in [0, {self.cameras}), got {camera!r}')
-        return int(camera)
-
     def set_plane(self, camera, points=None, matrix=None, bounds=None):
         """The floor of `camera`: `points`, at least four ((px, py), (X_mm, Y_mm)) pairs of original-image pixels and
         floor millimetres, all on one side of the horizon and, if there are only four, no three on a line (solved by
@@ -216,36 +212,10 @@ class GroundPlane:
         same keep tensor; give it to a consumer with scale_factor=None).  result, ids and scale_factor are what
         `ZoneMonitor.update_many` takes.  A camera without a plane places nobody.  One launch per 32 items on the
         current stream; no host copy, no sync."""
-        who = 'GroundPlane.update'
         items = list(items)
-        if any(not (isinstance(it, (tuple, list)) and len(it) == 3) for it in items):
-            raise ValueError(f'{who}: items are (camera, result, ids) triples')
-        if not items:
+        entries = self._entries(items, scale_factor, 'GroundPlane.update')
+        if not entries:
             return []
-        cams = [self._camera(c, who) for c, _, _ in items]
-        poses = [_poses(r, i, who) for i, (_, r, _) in enumerate(items)]
-        scales = _scales(scale_factor, len(items), who)
-        if any(not (0 < sx < float('inf') and 0 < sy < float('inf')) for sx, sy in scales):
-            raise ValueError(f'{who}: a scale factor must be positive and finite')
-        all_ids = []
-        for i, ((kpts, bboxes, keep), (_, _, ids)) in enumerate(zip(poses, items)):
-            if kpts.shape[1] != self.K:
-                raise ValueError(f'{who}: results[{i}] has K = {kpts.shape[1]}, the plane K = {self.K}')
-            if kpts.shape[0] > native.TRACK_MAX_POSES:
-                raise ValueError(f'{who}: results[{i}] has {kpts.shape[0]} poses, at most {native.TRACK_MAX_POSES}')
-            if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32
-                    and tuple(ids.shape) == (kpts.shape[0],)):
-                raise ValueError(f'{who}: ids of results[{i}] must be an int32 [{kpts.shape[0]}] tensor')
-            if not all(t is None or t.is_cuda for t in (kpts, bboxes, keep, ids)):
-                raise ValueError(f'{who}: results[{i}] and its ids must be HIP device tensors (pavenet_amd has no CPU '
-                                 'path)')
-            all_ids.append(ids.contiguous())
-        dev = poses[0][0].device
-        if self._state is not None and self._state['id'].device != dev:
-            raise ValueError(f"{who}: the plane's state is on {self._state['id'].device}, results[0] on {dev}")
-        entries = [(kp, bb, keep, ids, c, sc) for (kp, bb, keep), ids, c, sc in zip(poses, all_ids, cams, scales)]
-        if self._state is None:
-            self._allocate(dev)
         outs = ops.floor_update(entries, self._state, self._calib, K=self.K, velocity_gain=self.velocity_gain,
                                 near=self.near, unit=self.unit, origin=self.origin, max_age=self.max_age,
                                 anchor=self.anchor, anchor_kpts=self.anchor_kpts, score_thr=self.score_thr,
@@ -268,22 +238,13 @@ class GroundPlane:
     def reset(self, camera=None):
         """Frees the slots of `camera` (None: of every camera) and restarts its frame and drop counts at 0; its plane
         stays.  The state tensors stay where they are."""
-        if camera is not None:
-            camera = self._camera(camera, 'GroundPlane.reset')
-        if self._state is None:
-            return
-        c = slice(None) if camera is None else camera
-        for name in ('id', 'frame', 'dropped'):
-            self._state[name][c] = 0
+        self._reset(camera)
 
     def state(self, camera=0):
         """Views of one camera's slots on the device: id, last, hits, travel [S] (id 0 = free slot; its other fields
         mean nothing), pos [S, 2] (mm), vel [S, 2] (1/256 mm per frame), frame, dropped (0-d).  None before the first
         call."""
-        camera = self._camera(camera, 'GroundPlane.state')
-        if self._state is None:
-            return None
-        return {name: self._state[name][camera] for name in _STATE}
+        return self._views(camera, 'state', _STATE)
 
     def calibration(self, camera=0):
         """Views of one camera's calibration on the device, int64: G [3, 3] (1/8 pixel -> floor, times a power of

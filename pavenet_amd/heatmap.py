@@ -24,7 +24,8 @@ import torch
 
 from . import native, ops
 from .preprocess import NV12_MATRICES
-from .render import _bgr_triple, _poses, _scales, bgr_to_yuv
+from .render import _bgr_triple, bgr_to_yuv
+from .tracked import Tracked
 from .zones import ANKLES
 
 _STATE = ('id', 'last', 'cell', 'frame', 'dropped')
@@ -47,13 +48,15 @@ def _ramp():
 HEAT_PALETTE = _ramp()
 
 
-class FootfallMap:
+class FootfallMap(Tracked):
     """Footfall maps of `cameras` cameras over pictures of `size` = (width, height) original-image pixels (1 .. 8192
     each), one cell per `cell` x `cell` pixels (4, 8, 16, 32 or 64; at most 512 cells a side).  Who takes part, the
     slots (`max_tracks` 1 .. 128, freed after `max_age` frames unseen), `anchor`, `anchor_kpts`, `score_thr` and
     `kpt_thr` are ``ZoneMonitor``'s.  A pose adds (radius + 1 - |dx|)(radius + 1 - |dy|) to `dwell` at the cells within
     `radius` (0 .. 3) of its own, and 1 to `visits` at its own cell when its track comes into it.  Every `half_life`
     frames (0 .. 2^18; 0: never) both maps are halved."""
+    _NOUN, _NOUNS = 'the map', "the map's"
+    _RESET = ('id', 'frame', 'dropped', 'peak', 'dwell', 'visits')
 
     def __init__(self, K, size, cell=8, cameras=1, max_tracks=128, max_age=30, anchor='feet', anchor_kpts=None, radius=1,
                  half_life=0, score_thr=0.3, kpt_thr=0.):
@@ -95,46 +98,15 @@ class FootfallMap:
                            frame=torch.zeros((C,), **z), dropped=torch.zeros((C,), **z), peak=torch.zeros((C, 2), **z),
                            dwell=torch.zeros((C, self.Gh, self.Gw), **z), visits=torch.zeros((C, self.Gh, self.Gw), **z))
 
-    def _camera(self, camera, who):
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < self.cameras:
-            raise ValueError(f'{who}: camera must be an integer in [0, {self.cameras}), got {camera!r}')
-        return int(camera)
-
     def update_many(self, items, scale_factor=None):
         """items: (camera, result, ids) triples, the entries of one camera in time order -> one dict per item of new
         int32 [N] device tensors: cell (the pose's cell gy Gw + gx; -1: it takes no part or stands off the map), dwell
         and visits (the two maps at that cell after the frame, else 0).  result, ids and scale_factor are what
         `ZoneMonitor.update_many` takes.  One launch per 32 items on the current stream; no host copy, no sync."""
-        who = 'FootfallMap.update'
         items = list(items)
-        if any(not (isinstance(it, (tuple, list)) and len(it) == 3) for it in items):
-            raise ValueError(f'{who}: items are (camera, result, ids) triples')
-        if not items:
+        entries = self._entries(items, scale_factor, 'FootfallMap.update')
+        if not entries:
             return []
-        cams = [self._camera(c, who) for c, _, _ in items]
-        poses = [_poses(r, i, who) for i, (_, r, _) in enumerate(items)]
-        scales = _scales(scale_factor, len(items), who)
-        if any(not (0 < sx < float('inf') and 0 < sy < float('inf')) for sx, sy in scales):
-            raise ValueError(f'{who}: a scale factor must be positive and finite')
-        all_ids = []
-        for i, ((kpts, bboxes, keep), (_, _, ids)) in enumerate(zip(poses, items)):
-            if kpts.shape[1] != self.K:
-                raise ValueError(f'{who}: results[{i}] has K = {kpts.shape[1]}, the map K = {self.K}')
-            if kpts.shape[0] > native.TRACK_MAX_POSES:
-                raise ValueError(f'{who}: results[{i}] has {kpts.shape[0]} poses, at most {native.TRACK_MAX_POSES}')
-            if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32
-                    and tuple(ids.shape) == (kpts.shape[0],)):
-                raise ValueError(f'{who}: ids of results[{i}] must be an int32 [{kpts.shape[0]}] tensor')
-            if not all(t is None or t.is_cuda for t in (kpts, bboxes, keep, ids)):
-                raise ValueError(f'{who}: results[{i}] and its ids must be HIP device tensors (pavenet_amd has no CPU '
-                                 'path)')
-            all_ids.append(ids.contiguous())
-        dev = poses[0][0].device
-        if self._state is not None and self._state['id'].device != dev:
-            raise ValueError(f"{who}: the map's state is on {self._state['id'].device}, results[0] on {dev}")
-        entries = [(kp, bb, keep, ids, c, sc) for (kp, bb, keep), ids, c, sc in zip(poses, all_ids, cams, scales)]
-        if self._state is None:
-            self._allocate(dev)
         return ops.heat_update(entries, self._state, K=self.K, size=self.size, cell=self.cell, radius=self.radius,
                                half_life=self.half_life, max_age=self.max_age, anchor=self.anchor,
                                anchor_kpts=self.anchor_kpts, score_thr=self.score_thr, kpt_thr=self.kpt_thr)
@@ -146,29 +118,17 @@ class FootfallMap:
     def reset(self, camera=None):
         """Clears the maps and the peak of `camera` (None: of every camera), frees its slots and restarts its frame
         and drop counts at 0.  The state tensors stay where they are."""
-        if camera is not None:
-            camera = self._camera(camera, 'FootfallMap.reset')
-        if self._state is None:
-            return
-        c = slice(None) if camera is None else camera
-        for name in ('id', 'frame', 'dropped', 'peak', 'dwell', 'visits'):
-            self._state[name][c] = 0
+        self._reset(camera)
 
     def maps(self, camera=0):
         """Views of one camera's maps on the device: dwell, visits [Gh, Gw] and peak [2] (their maxima), int32.  None
         before the first call."""
-        camera = self._camera(camera, 'FootfallMap.maps')
-        if self._state is None:
-            return None
-        return {name: self._state[name][camera] for name in ('dwell', 'visits', 'peak')}
+        return self._views(camera, 'maps', ('dwell', 'visits', 'peak'))
 
     def state(self, camera=0):
         """Views of one camera's slots on the device: id, last, cell [S] (id 0 = free slot; its other fields mean
         nothing; cell -1 = off the map), frame, dropped (0-d).  None before the first call."""
-        camera = self._camera(camera, 'FootfallMap.state')
-        if self._state is None:
-            return None
-        return {name: self._state[name][camera] for name in _STATE}
+        return self._views(camera, 'state', _STATE)
 
     def device_tensors(self):
         """The whole tensors a reader on the device needs, for every camera at once and read only: dwell, visits

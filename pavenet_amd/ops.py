@@ -899,6 +899,89 @@ def track_poses(entries, state, scratch, C, *, min_kpts, max_age=30, score_thr=0
     return ids
 
 
+ZONE_ANCHORS = ('feet', 'box', 'centre')       # PAVE_ZONE_ANCHOR_*
+
+
+# ---- what the six updates that follow track ids share (csrc/pave_tracked.h) ----
+def _tracked_entries(who, entries, K, cameras):
+    """The (kpts, bboxes, keep, ids, camera, sx, sy, N) of every (kpts, bboxes, keep, ids, camera, (sx, sy)) entry of
+    an update that follows track ids, or the ValueError."""
+    checked = []
+    for i, entry in enumerate(entries):
+        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
+            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
+        kpts, bboxes, keep, ids, camera, scale = entry
+        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
+                and tuple(kpts.shape[1:]) == (K, 3)):
+            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
+        N = kpts.shape[0]
+        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
+            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
+        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
+                                     and tuple(keep.shape) == (N,)):
+            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
+            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
+        if N > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+        try:
+            sx, sy = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
+        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
+            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
+        if not (kpts.is_contiguous() and bboxes.is_contiguous() and ids.is_contiguous()
+                and (keep is None or keep.is_contiguous())):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
+        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    return checked
+
+
+def _max_age(who, max_age):
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
+        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    return int(max_age)
+
+
+def _anchor(who, anchor, anchor_kpts, K):
+    """(PAVE_ZONE_ANCHOR_*, the key points of 'feet') of an update that places a pose by its anchor."""
+    if anchor not in ZONE_ANCHORS:
+        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
+    anchor_kpts = list(anchor_kpts)
+    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
+            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
+        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
+                         f'{anchor_kpts!r}')
+    return ZONE_ANCHORS.index(anchor), anchor_kpts
+
+
+def _tracked_devices(who, dev, tensors, checked, what='the state tensors'):
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(t.device != dev for t in tensors):
+        raise ValueError(f'{who}: {what} must be on one device ({dev})')
+    for i, c in enumerate(checked):   # (spelt out: this runs per entry of every call)
+        if c[0].device != dev or c[1].device != dev or c[3].device != dev or (c[2] is not None and c[2].device != dev):
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+
+
+def _tracked_fill(plan, part, cameras, S, K, max_age, score_thr, kpt_thr, anchor=None):
+    """The fields every plan of these updates has: the entries of _tracked_entries, the sizes, who takes part and,
+    where the plan has one, the anchor of _anchor."""
+    for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
+        plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
+            _ptr(keep) or None, _ptr(ids) or None
+        plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
+    plan.entries, plan.cameras, plan.S, plan.K, plan.max_age = len(part), cameras, S, K, max_age
+    plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+    if anchor is not None:
+        plan.anchor, plan.n_anchor = anchor[0], len(anchor[1])
+        for i, k in enumerate(anchor[1]):
+            plan.anchor_kpt[i] = k
+
+
 _SMOOTH_STATE = (('id', 1), ('last', 1), ('pos', 2), ('vel', 2), ('frame', 0), ('dropped', 0))
 # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, K + 2, 2]
 
@@ -933,60 +1016,21 @@ def smooth_poses(entries, state, *, max_age=30, alpha_min=32, beta=128, velocity
                             ('velocity_gain', velocity_gain, 1, 16)):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
             raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
-        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
-    checked = []
-    for i, entry in enumerate(entries):
-        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
-            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
-        kpts, bboxes, keep, ids, camera, scale = entry
-        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
-                and tuple(kpts.shape[1:]) == (K, 3)):
-            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
-        N = kpts.shape[0]
-        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
-            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
-        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
-                                     and tuple(keep.shape) == (N,)):
-            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
-        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
-            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
-        if N > native.TRACK_MAX_POSES:
-            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
-            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
-        try:
-            sx, sy = (float(v) for v in scale)
-        except (TypeError, ValueError):
-            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
-        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
-            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
-        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
-            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
-        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    max_age = _max_age(who, max_age)
+    checked = _tracked_entries(who, entries, K, cameras)
     # the shapes are right: now where the tensors live
-    if not dev.type == 'cuda':
-        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
-    if any(state[n].device != dev for n, _ in _SMOOTH_STATE):
-        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
-    for i, c in enumerate(checked):
-        if any(t is not None and t.device != dev for t in c[:4]):
-            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    _tracked_devices(who, dev, (state[n] for n, _ in _SMOOTH_STATE), checked)
     outs = [(torch.empty((c[7], K, 3), dtype=torch.float32, device=dev),
              torch.empty((c[7], 5), dtype=torch.float32, device=dev)) for c in checked]
     for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
         plan = native.SmoothPlan()
         part = checked[at:at + native.TRACK_MAX_FRAMES]
-        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
-            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
-                _ptr(keep) or None, _ptr(ids) or None
+        _tracked_fill(plan, part, cameras, S, K, max_age, score_thr, kpt_thr)
+        for i in range(len(part)):
             plan.out_kpts[i], plan.out_bboxes[i] = (t.data_ptr() or None for t in outs[at + i])
-            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
         plan.slot_id, plan.slot_last, plan.slot_pos, plan.slot_vel, plan.frame, plan.dropped = (
             state[n].data_ptr() for n, _ in _SMOOTH_STATE)
-        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
-        plan.alpha_min, plan.beta, plan.velocity_gain, plan.max_age = alpha_min, beta, velocity_gain, int(max_age)
-        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        plan.alpha_min, plan.beta, plan.velocity_gain = alpha_min, beta, velocity_gain
         _launch('pave_smooth_poses', who, dev, ctypes.byref(plan))
     return outs
 
@@ -994,7 +1038,6 @@ def smooth_poses(entries, state, *, max_age=30, alpha_min=32, beta=128, velocity
 _ZONE_STATE = (('id', 1), ('last', 1), ('pos', 2), ('inside', 1), ('alerted', 1), ('streak', 3), ('since', 3),
                ('frame', 0), ('dropped', 0), ('counters', 4), ('geometry', 5))
 # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 8], 4 [cameras, 56], 5 [cameras, 306]
-ZONE_ANCHORS = ('feet', 'box', 'centre')       # PAVE_ZONE_ANCHOR_*
 
 
 def zone_events(entries, state, *, K, max_age=30, anchor='feet', anchor_kpts=(), min_frames=2, max_events=256,
@@ -1031,52 +1074,11 @@ def zone_events(entries, state, *, K, max_age=30, anchor='feet', anchor_kpts=(),
     for name, v, lo, hi in (('min_frames', min_frames, 1, 255), ('max_events', max_events, 1, native.ZONE_MAX_EVENTS)):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
             raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
-        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
-    if anchor not in ZONE_ANCHORS:
-        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
-    anchor_kpts = list(anchor_kpts)
-    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
-            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
-        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
-                         f'{anchor_kpts!r}')
-    checked = []
-    for i, entry in enumerate(entries):
-        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
-            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
-        kpts, bboxes, keep, ids, camera, scale = entry
-        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
-                and tuple(kpts.shape[1:]) == (K, 3)):
-            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
-        N = kpts.shape[0]
-        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
-            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
-        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
-                                     and tuple(keep.shape) == (N,)):
-            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
-        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
-            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
-        if N > native.TRACK_MAX_POSES:
-            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
-            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
-        try:
-            sx, sy = (float(v) for v in scale)
-        except (TypeError, ValueError):
-            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
-        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
-            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
-        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
-            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
-        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    max_age = _max_age(who, max_age)
+    anchor = _anchor(who, anchor, anchor_kpts, K)
+    checked = _tracked_entries(who, entries, K, cameras)
     # the shapes are right: now where the tensors live
-    if not dev.type == 'cuda':
-        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
-    if any(state[n].device != dev for n, _ in _ZONE_STATE):
-        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
-    for i, c in enumerate(checked):
-        if any(t is not None and t.device != dev for t in c[:4]):
-            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    _tracked_devices(who, dev, (state[n] for n, _ in _ZONE_STATE), checked)
     z = dict(dtype=torch.int32, device=dev)
     outs = [dict(zones=torch.empty((c[7],), **z), dwell=torch.empty((c[7], native.ZONE_MAX_ZONES), **z),
                  events=torch.empty((max_events, native.ZONE_EVENT_WORDS), **z), n_events=torch.empty((), **z))
@@ -1084,22 +1086,15 @@ def zone_events(entries, state, *, K, max_age=30, anchor='feet', anchor_kpts=(),
     for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
         plan = native.ZonePlan()
         part = checked[at:at + native.TRACK_MAX_FRAMES]
-        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
-            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
-                _ptr(keep) or None, _ptr(ids) or None
+        _tracked_fill(plan, part, cameras, S, K, max_age, score_thr, kpt_thr, anchor)
+        for i in range(len(part)):
             out = outs[at + i]
             plan.out_zones[i], plan.out_dwell[i] = out['zones'].data_ptr() or None, out['dwell'].data_ptr() or None
             plan.out_events[i], plan.out_n_events[i] = out['events'].data_ptr(), out['n_events'].data_ptr()
-            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
         (plan.slot_id, plan.slot_last, plan.slot_pos, plan.slot_inside, plan.slot_alerted, plan.slot_streak,
          plan.slot_since, plan.frame, plan.dropped, plan.counters, plan.geometry) = (
             state[n].data_ptr() for n, _ in _ZONE_STATE)
-        for i, k in enumerate(anchor_kpts):
-            plan.anchor_kpt[i] = k
-        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
-        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
-        plan.min_frames, plan.max_events, plan.max_age = min_frames, max_events, int(max_age)
-        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        plan.min_frames, plan.max_events = min_frames, max_events
         _launch('pave_zone_events', who, dev, ctypes.byref(plan))
     return outs
 
@@ -1148,8 +1143,7 @@ def posture_events(entries, state, *, K, parts, max_age=30, min_frames=3, lean=1
                             ('down_frames', down_frames, 0, native.POSTURE_MAX_WAIT)):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
             raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
-        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
+    max_age = _max_age(who, max_age)
     try:
         parts = [list(p) for p in parts]
     except TypeError:
@@ -1161,43 +1155,9 @@ def posture_events(entries, state, *, K, parts, max_age=30, min_frames=3, lean=1
                 isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in p):
             raise ValueError(f'{who}: part {name} holds at most {native.POSTURE_MAX_PART} integers in [0, {K}), got '
                              f'{p!r}')
-    checked = []
-    for i, entry in enumerate(entries):
-        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
-            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
-        kpts, bboxes, keep, ids, camera, scale = entry
-        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
-                and tuple(kpts.shape[1:]) == (K, 3)):
-            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
-        N = kpts.shape[0]
-        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
-            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
-        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
-                                     and tuple(keep.shape) == (N,)):
-            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
-        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
-            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
-        if N > native.TRACK_MAX_POSES:
-            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
-            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
-        try:
-            sx, sy = (float(v) for v in scale)
-        except (TypeError, ValueError):
-            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
-        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
-            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
-        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
-            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
-        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
+    checked = _tracked_entries(who, entries, K, cameras)
     # the shapes are right: now where the tensors live
-    if not dev.type == 'cuda':
-        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
-    if any(state[n].device != dev for n, _ in _POSTURE_STATE):
-        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
-    for i, c in enumerate(checked):
-        if any(t is not None and t.device != dev for t in c[:4]):
-            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    _tracked_devices(who, dev, (state[n] for n, _ in _POSTURE_STATE), checked)
     z = dict(dtype=torch.int32, device=dev)
     outs = [dict(posture=torch.empty((c[7],), **z), raw=torch.empty((c[7],), **z), hands=torch.empty((c[7],), **z),
                  since=torch.empty((c[7],), **z), events=torch.empty((max_events, native.POSTURE_EVENT_WORDS), **z),
@@ -1205,14 +1165,12 @@ def posture_events(entries, state, *, K, parts, max_age=30, min_frames=3, lean=1
     for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
         plan = native.PosturePlan()
         part = checked[at:at + native.TRACK_MAX_FRAMES]
-        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
-            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
-                _ptr(keep) or None, _ptr(ids) or None
+        _tracked_fill(plan, part, cameras, S, K, max_age, score_thr, kpt_thr)
+        for i in range(len(part)):
             out = outs[at + i]
             plan.out_posture[i], plan.out_raw[i] = out['posture'].data_ptr() or None, out['raw'].data_ptr() or None
             plan.out_hands[i], plan.out_since[i] = out['hands'].data_ptr() or None, out['since'].data_ptr() or None
             plan.out_events[i], plan.out_n_events[i] = out['events'].data_ptr(), out['n_events'].data_ptr()
-            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
         (plan.slot_id, plan.slot_last, plan.slot_posture, plan.slot_since, plan.slot_upright, plan.slot_streak,
          plan.slot_alerted, plan.slot_hands, plan.slot_hand_streak, plan.frame, plan.dropped, plan.counters) = (
             state[n].data_ptr() for n, _ in _POSTURE_STATE)
@@ -1220,12 +1178,9 @@ def posture_events(entries, state, *, K, parts, max_age=30, min_frames=3, lean=1
             plan.n_part[p] = len(keys)
             for i, k in enumerate(keys):
                 plan.part[p][i] = k
-        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
         plan.min_frames, plan.lean, plan.flat, plan.squat = min_frames, lean, flat, squat
         plan.hand_up = native.POSTURE_HANDS_OFF if hand_up is None else hand_up
-        plan.fall_window, plan.down_frames, plan.max_events, plan.max_age = fall_window, down_frames, max_events, \
-            int(max_age)
-        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        plan.fall_window, plan.down_frames, plan.max_events = fall_window, down_frames, max_events
         _launch('pave_posture_events', who, dev, ctypes.byref(plan))
     return outs
 
@@ -1397,41 +1352,6 @@ def _heat_state(who, state, names, size, cell):
     return cameras, S, Gw, Gh
 
 
-def _tracked_entries(who, entries, K, cameras):
-    """The (kpts, bboxes, keep, ids, camera, sx, sy, N) of every (kpts, bboxes, keep, ids, camera, (sx, sy)) entry of
-    an update that follows track ids, or the ValueError."""
-    checked = []
-    for i, entry in enumerate(entries):
-        if not (isinstance(entry, (tuple, list)) and len(entry) == 6):
-            raise ValueError(f'{who}: entry {i} is (kpts, bboxes, keep, ids, camera, (sx, sy))')
-        kpts, bboxes, keep, ids, camera, scale = entry
-        if not (isinstance(kpts, torch.Tensor) and kpts.dtype == torch.float32 and kpts.dim() == 3
-                and tuple(kpts.shape[1:]) == (K, 3)):
-            raise ValueError(f'{who}: kpts of entry {i} must be a [N, {K}, 3] float32 tensor')
-        N = kpts.shape[0]
-        if not (isinstance(bboxes, torch.Tensor) and bboxes.dtype == torch.float32 and tuple(bboxes.shape) == (N, 5)):
-            raise ValueError(f'{who}: bboxes of entry {i} must be a [{N}, 5] float32 tensor')
-        if keep is not None and not (isinstance(keep, torch.Tensor) and keep.dtype == torch.int32
-                                     and tuple(keep.shape) == (N,)):
-            raise ValueError(f'{who}: keep of entry {i} must be a [{N}] int32 tensor')
-        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
-            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
-        if N > native.TRACK_MAX_POSES:
-            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
-            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
-        try:
-            sx, sy = (float(v) for v in scale)
-        except (TypeError, ValueError):
-            raise ValueError(f'{who}: the scale of entry {i} is (sx, sy)') from None
-        if not (0 < sx < float('inf') and 0 < sy < float('inf')):
-            raise ValueError(f'{who}: the scale of entry {i} must be positive and finite, got {(sx, sy)}')
-        if any(t is not None and not t.is_contiguous() for t in (kpts, bboxes, keep, ids)):
-            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
-        checked.append((kpts, bboxes, keep, ids, int(camera), sx, sy, N))
-    return checked
-
-
 def heat_update(entries, state, *, K, size, cell=8, radius=1, half_life=0, max_age=30, anchor='feet', anchor_kpts=(),
                 score_thr=0.3, kpt_thr=0.):
     """Footfall maps from frames of tracked poses, one launch per 32 frames (pave_heat_update; the rule is DESIGN
@@ -1450,47 +1370,27 @@ def heat_update(entries, state, *, K, size, cell=8, radius=1, half_life=0, max_a
                             ('half_life', half_life, 0, native.HEAT_MAX_HALF_LIFE)):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
             raise ValueError(f'{who}: {name} must be an integer in {lo} .. {hi}, got {v!r}')
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
-        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
-    if anchor not in ZONE_ANCHORS:
-        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
-    anchor_kpts = list(anchor_kpts)
-    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
-            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
-        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
-                         f'{anchor_kpts!r}')
+    max_age = _max_age(who, max_age)
+    anchor = _anchor(who, anchor, anchor_kpts, K)
     checked = _tracked_entries(who, entries, K, cameras)
     # the shapes are right: now where the tensors live
     dev = state['peak'].device
-    if not dev.type == 'cuda':
-        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
-    if any(state[n].device != dev for n, _ in _HEAT_STATE):
-        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
-    for i, c in enumerate(checked):
-        if any(t is not None and t.device != dev for t in c[:4]):
-            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    _tracked_devices(who, dev, (state[n] for n, _ in _HEAT_STATE), checked)
     z = dict(dtype=torch.int32, device=dev)
     outs = [dict(cell=torch.empty((c[7],), **z), dwell=torch.empty((c[7],), **z), visits=torch.empty((c[7],), **z))
             for c in checked]
     for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
         plan = native.HeatPlan()
         part = checked[at:at + native.TRACK_MAX_FRAMES]
-        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
-            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
-                _ptr(keep) or None, _ptr(ids) or None
+        _tracked_fill(plan, part, cameras, S, K, max_age, score_thr, kpt_thr, anchor)
+        for i in range(len(part)):
             out = outs[at + i]
             plan.out_cell[i], plan.out_dwell[i], plan.out_visits[i] = (out[n].data_ptr() or None
                                                                        for n in ('cell', 'dwell', 'visits'))
-            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
         (plan.slot_id, plan.slot_last, plan.slot_cell, plan.frame, plan.dropped, plan.peak, plan.dwell, plan.visits) = (
             state[n].data_ptr() for n, _ in _HEAT_STATE)
-        for i, k in enumerate(anchor_kpts):
-            plan.anchor_kpt[i] = k
-        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
-        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
         plan.width, plan.height, plan.cell, plan.radius = int(size[0]), int(size[1]), cell, radius
-        plan.half_life, plan.max_age = half_life, int(max_age)
-        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        plan.half_life = half_life
         _launch('pave_heat_update', who, dev, ctypes.byref(plan))
     return outs
 
@@ -1639,45 +1539,25 @@ def trail_update(entries, state, *, K, stride=1, min_step=16, max_age=30, anchor
     cameras, S, L = _trail_state(who, state, [n for n, _ in _TRAIL_STATE])
     _int_in(who, 'stride', stride, 1, native.TRAIL_MAX_STRIDE)
     _int_in(who, 'min_step', min_step, 0, native.TRAIL_MAX_STEP)
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
-        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
-    if anchor not in ZONE_ANCHORS:
-        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
-    anchor_kpts = list(anchor_kpts)
-    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
-            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
-        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
-                         f'{anchor_kpts!r}')
+    max_age = _max_age(who, max_age)
+    anchor = _anchor(who, anchor, anchor_kpts, K)
     checked = _tracked_entries(who, entries, K, cameras)
     # the shapes are right: now where the tensors live
     dev = state['when'].device
-    if not dev.type == 'cuda':
-        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
-    if any(state[n].device != dev for n, _ in _TRAIL_STATE):
-        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
-    for i, c in enumerate(checked):
-        if any(t is not None and t.device != dev for t in c[:4]):
-            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    _tracked_devices(who, dev, (state[n] for n, _ in _TRAIL_STATE), checked)
     names = ('count', 'span', 'dist', 'path')
     outs = [{n: torch.empty((c[7],), dtype=torch.int32, device=dev) for n in names} for c in checked]
     for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
         plan = native.TrailPlan()
         part = checked[at:at + native.TRACK_MAX_FRAMES]
-        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
-            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
-                _ptr(keep) or None, _ptr(ids) or None
+        _tracked_fill(plan, part, cameras, S, K, max_age, score_thr, kpt_thr, anchor)
+        for i in range(len(part)):
             out = outs[at + i]
             plan.out_count[i], plan.out_span[i], plan.out_dist[i], plan.out_path[i] = (out[n].data_ptr() or None
                                                                                        for n in names)
-            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
         (plan.slot_id, plan.slot_last, plan.slot_pos, plan.slot_head, plan.slot_count, plan.slot_box, plan.pts, plan.when,
          plan.frame, plan.dropped) = (state[n].data_ptr() for n, _ in _TRAIL_STATE)
-        for i, k in enumerate(anchor_kpts):
-            plan.anchor_kpt[i] = k
-        plan.entries, plan.cameras, plan.S, plan.K, plan.L = len(part), cameras, S, K, L
-        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
-        plan.stride, plan.min_step, plan.max_age = stride, min_step, int(max_age)
-        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
+        plan.L, plan.stride, plan.min_step = L, stride, min_step
         _launch('pave_trail_update', who, dev, ctypes.byref(plan))
     return outs
 
@@ -1783,45 +1663,25 @@ def floor_update(entries, state, calib, *, K, velocity_gain=4, near=1500, unit=1
         raise ValueError(f'{who}: origin is (x, y) in mm, got {origin!r}')
     for v in origin:
         _int_in(who, 'origin', v, -native.FLOOR_MAX_MM, native.FLOOR_MAX_MM)
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0:
-        raise ValueError(f'{who}: max_age must be an integer >= 0, got {max_age!r}')
-    if anchor not in ZONE_ANCHORS:
-        raise ValueError(f'{who}: anchor must be one of {", ".join(ZONE_ANCHORS)}, got {anchor!r}')
-    anchor_kpts = list(anchor_kpts)
-    if len(anchor_kpts) > native.ZONE_MAX_ANCHOR_KPTS or any(
-            isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < K for k in anchor_kpts):
-        raise ValueError(f'{who}: anchor_kpts holds at most {native.ZONE_MAX_ANCHOR_KPTS} integers in [0, {K}), got '
-                         f'{anchor_kpts!r}')
+    max_age = _max_age(who, max_age)
+    anchor = _anchor(who, anchor, anchor_kpts, K)
     checked = _tracked_entries(who, entries, K, cameras)
     # the shapes are right: now where the tensors live
     dev = state['id'].device
-    if not dev.type == 'cuda':
-        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
-    if any(state[n].device != dev for n in names) or calib.device != dev:
-        raise ValueError(f'{who}: the state tensors and calib must be on one device ({dev})')
-    for i, c in enumerate(checked):
-        if any(t is not None and t.device != dev for t in c[:4]):
-            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    _tracked_devices(who, dev, [calib] + [state[n] for n in names], checked, 'the state tensors and calib')
     words = [torch.empty((native.FLOOR_OUT_WORDS * c[7],), dtype=torch.int32, device=dev) for c in checked]
     floats = [torch.empty((c[7] * (K * 3 + 5),), dtype=torch.float32, device=dev) for c in checked]
     for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
         plan = native.FloorPlan()
         part = checked[at:at + native.TRACK_MAX_FRAMES]
-        for i, (kpts, bboxes, keep, ids, camera, sx, sy, N) in enumerate(part):
-            plan.kpts[i], plan.bboxes[i], plan.keep[i], plan.ids[i] = _ptr(kpts) or None, _ptr(bboxes) or None, \
-                _ptr(keep) or None, _ptr(ids) or None
+        _tracked_fill(plan, part, cameras, S, K, max_age, score_thr, kpt_thr, anchor)
+        for i in range(len(part)):
             plan.out[i], plan.out_floor[i] = words[at + i].data_ptr() or None, floats[at + i].data_ptr() or None
-            plan.n[i], plan.camera[i], plan.scale[i][0], plan.scale[i][1] = N, camera, sx, sy
         (plan.slot_id, plan.slot_last, plan.slot_hits, plan.slot_pos, plan.slot_vel, plan.slot_travel, plan.frame,
          plan.dropped) = (state[n].data_ptr() for n in names)
         plan.calib = calib.data_ptr()
-        for i, k in enumerate(anchor_kpts):
-            plan.anchor_kpt[i] = k
-        plan.entries, plan.cameras, plan.S, plan.K = len(part), cameras, S, K
-        plan.anchor, plan.n_anchor = ZONE_ANCHORS.index(anchor), len(anchor_kpts)
-        plan.velocity_gain, plan.near, plan.unit, plan.max_age = velocity_gain, near, unit, int(max_age)
+        plan.velocity_gain, plan.near, plan.unit = velocity_gain, near, unit
         plan.origin_x, plan.origin_y = origin
-        plan.score_thr, plan.kpt_thr = float(score_thr), float(kpt_thr)
         _launch('pave_floor_update', who, dev, ctypes.byref(plan))
     outs = []
     for c, w, f in zip(checked, words, floats):

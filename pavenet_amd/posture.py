@@ -15,7 +15,7 @@ learned classifier.
 import torch
 
 from . import native, ops
-from .render import _poses, _scales
+from .tracked import Tracked
 
 UNKNOWN, UPRIGHT, LOW, LEANING, LYING = (
     native.DEFINES['PAVE_POSTURE_' + n] for n in ('UNKNOWN', 'UPRIGHT', 'LOW', 'LEANING', 'LYING'))
@@ -33,7 +33,7 @@ _SLOTS = ('id', 'last', 'posture', 'since', 'upright', 'streak', 'alerted', 'han
 _STATE = _SLOTS + ('frame', 'dropped')
 
 
-class PostureMonitor:
+class PostureMonitor(Tracked):
     """Classes the tracked poses of `cameras` cameras by the slope of the trunk: one slot per track id (`max_tracks`,
     1 .. 128; a slot not seen for more than `max_age` frames is freed).  A pose takes part iff its box score is >
     `score_thr` (and keep, and finite coordinates), its id is >= 1 and no pose before it in the frame has the same id.
@@ -47,6 +47,8 @@ class PostureMonitor:
     disagreed `min_frames` (1 .. 255) frames in a row.  LYING within `fall_window` frames of UPRIGHT is a fall, and
     `down_frames` frames of LYING are reported once per stay (0: never).  `max_events` (1 .. 4096) rows of events
     are stored per frame, and all of them are counted."""
+    _NOUN, _NOUNS = 'the monitor', "the monitor's"
+    _RESET = ('id', 'frame', 'dropped', 'counters')
 
     def __init__(self, K, cameras=1, max_tracks=128, max_age=30, parts=None, min_frames=3, lean=11, flat=11, squat=18,
                  hand_up=4, fall_window=30, down_frames=75, max_events=256, score_thr=0.3, kpt_thr=0.):
@@ -95,11 +97,6 @@ class PostureMonitor:
         self._state.update(frame=torch.zeros((C,), **z), dropped=torch.zeros((C,), **z),
                            counters=torch.zeros((C, native.POSTURE_COUNTER_WORDS), **z))
 
-    def _camera(self, camera, who):
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < self.cameras:
-            raise ValueError(f'{who}: camera must be an integer in [0, {self.cameras}), got {camera!r}')
-        return int(camera)
-
     def update_many(self, items, scale_factor=None):
         """items: (camera, result, ids) triples, the entries of one camera in time order -> one dict per item of new
         int32 device tensors: posture [N] (the debounced posture of the pose's track, UNKNOWN .. LYING; -1: the pose
@@ -107,36 +104,10 @@ class PostureMonitor:
         (frames in the current posture), events [max_events, 5] (rows (kind, index, id, pose, frame) in the rule's
         order; zero past the count) and n_events (0-d: all events of the frame, stored or not).  result, ids and
         scale_factor are what `ZoneMonitor.update_many` takes.  One launch per 32 items."""
-        who = 'PostureMonitor.update'
         items = list(items)
-        if any(not (isinstance(it, (tuple, list)) and len(it) == 3) for it in items):
-            raise ValueError(f'{who}: items are (camera, result, ids) triples')
-        if not items:
+        entries = self._entries(items, scale_factor, 'PostureMonitor.update')
+        if not entries:
             return []
-        cams = [self._camera(c, who) for c, _, _ in items]
-        poses = [_poses(r, i, who) for i, (_, r, _) in enumerate(items)]
-        scales = _scales(scale_factor, len(items), who)
-        if any(not (0 < sx < float('inf') and 0 < sy < float('inf')) for sx, sy in scales):
-            raise ValueError(f'{who}: a scale factor must be positive and finite')
-        all_ids = []
-        for i, ((kpts, bboxes, keep), (_, _, ids)) in enumerate(zip(poses, items)):
-            if kpts.shape[1] != self.K:
-                raise ValueError(f'{who}: results[{i}] has K = {kpts.shape[1]}, the monitor K = {self.K}')
-            if kpts.shape[0] > native.TRACK_MAX_POSES:
-                raise ValueError(f'{who}: results[{i}] has {kpts.shape[0]} poses, at most {native.TRACK_MAX_POSES}')
-            if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32
-                    and tuple(ids.shape) == (kpts.shape[0],)):
-                raise ValueError(f'{who}: ids of results[{i}] must be an int32 [{kpts.shape[0]}] tensor')
-            if not all(t is None or t.is_cuda for t in (kpts, bboxes, keep, ids)):
-                raise ValueError(f'{who}: results[{i}] and its ids must be HIP device tensors (pavenet_amd has no CPU '
-                                 'path)')
-            all_ids.append(ids.contiguous())
-        dev = poses[0][0].device
-        if self._state is not None and self._state['id'].device != dev:
-            raise ValueError(f"{who}: the monitor's state is on {self._state['id'].device}, results[0] on {dev}")
-        entries = [(kp, bb, keep, ids, c, sc) for (kp, bb, keep), ids, c, sc in zip(poses, all_ids, cams, scales)]
-        if self._state is None:
-            self._allocate(dev)
         return ops.posture_events(entries, self._state, K=self.K, parts=[self.parts[n] for n in PART_NAMES],
                                   max_age=self.max_age, min_frames=self.min_frames, lean=self.lean, flat=self.flat,
                                   squat=self.squat, hand_up=self.hand_up, fall_window=self.fall_window,
@@ -151,13 +122,7 @@ class PostureMonitor:
         """Frees the slots of `camera` (None: of every camera) without events; its frame count, drop count and
         counters restart at 0.  The state tensors stay where they are (a birth writes a slot, and a free slot is
         never read)."""
-        if camera is not None:
-            camera = self._camera(camera, 'PostureMonitor.reset')
-        if self._state is None:
-            return
-        c = slice(None) if camera is None else camera
-        for name in ('id', 'frame', 'dropped', 'counters'):
-            self._state[name][c] = 0
+        self._reset(camera)
 
     def counts(self, camera=0):
         """Views of one camera's running counters on the device: now [5] (the live slots per posture, UNKNOWN ..
@@ -174,10 +139,7 @@ class PostureMonitor:
         """Views of one camera's state on the device: id, last, posture, since, upright, streak, alerted, hands,
         hand_streak [S] (id 0 = free slot; its other fields mean nothing), frame, dropped (0-d).  None before the
         first call."""
-        camera = self._camera(camera, 'PostureMonitor.state')
-        if self._state is None:
-            return None
-        return {name: self._state[name][camera] for name in _STATE}
+        return self._views(camera, 'state', _STATE)
 
 
 def events_to_list(out):

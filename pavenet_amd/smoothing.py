@@ -13,10 +13,12 @@ scores.
 import torch
 
 from . import native, ops
-from .render import _poses, _scales
+from .tracked import Tracked
+
+_STATE = ('id', 'last', 'pos', 'vel', 'frame', 'dropped')
 
 
-class PoseSmoother:
+class PoseSmoother(Tracked):
     """Filters the K key points and the box corners of tracked poses over the frames of `cameras` cameras.  A camera
     keeps `max_tracks` (1 .. 128) slots, one per track id; a slot not seen for more than `max_age` frames is freed.
     A pose is filtered iff its box score is > `score_thr` (and keep, and finite coordinates), its id is >= 1 and no
@@ -27,6 +29,7 @@ class PoseSmoother:
     `beta` u / 16), u the point's smoothed speed in 1/1024 of the pose's size per frame: `alpha_min` (1 .. 256) is
     the gain at rest (256: no filter), `beta` (0 .. 4096) how fast a moving point gets its detection back (0: a fixed
     exponential filter), `velocity_gain` / 16 (1 .. 16) the weight of the newest frame in the speed."""
+    _NOUN, _NOUNS = 'the smoother', "the smoother's"
 
     def __init__(self, K, cameras=1, max_tracks=128, max_age=30, alpha_min=32, beta=128, velocity_gain=3,
                  score_thr=0.3, kpt_thr=0.):
@@ -53,47 +56,16 @@ class PoseSmoother:
                            pos=torch.zeros((C, S, J, 2), **z), vel=torch.zeros((C, S, J, 2), **z),
                            frame=torch.zeros((C,), **z), dropped=torch.zeros((C,), **z))
 
-    def _camera(self, camera, who):
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < self.cameras:
-            raise ValueError(f'{who}: camera must be an integer in [0, {self.cameras}), got {camera!r}')
-        return int(camera)
-
     def smooth_many(self, items, scale_factor=None):
         """items: (camera, result, ids) triples, the entries of one camera in time order -> one result per item, in
         the form it was given: (bboxes, labels, kpts) with the same labels tensor, or dict(bboxes=, kpts=, keep=)
         with the same keep tensor.  ids: the int32 [N] device tensor `PoseTracker.update` returned for the result.
         scale_factor: what the tracker was given (None for results made with rescale=True); the results that come
         back are in original-image pixels.  One launch per 32 items."""
-        who = 'PoseSmoother.smooth'
         items = list(items)
-        if any(not (isinstance(it, (tuple, list)) and len(it) == 3) for it in items):
-            raise ValueError(f'{who}: items are (camera, result, ids) triples')
-        if not items:
+        entries = self._entries(items, scale_factor, 'PoseSmoother.smooth')
+        if not entries:
             return []
-        cams = [self._camera(c, who) for c, _, _ in items]
-        poses = [_poses(r, i, who) for i, (_, r, _) in enumerate(items)]
-        scales = _scales(scale_factor, len(items), who)
-        if any(not (0 < sx < float('inf') and 0 < sy < float('inf')) for sx, sy in scales):
-            raise ValueError(f'{who}: a scale factor must be positive and finite')
-        all_ids = []
-        for i, ((kpts, bboxes, keep), (_, _, ids)) in enumerate(zip(poses, items)):
-            if kpts.shape[1] != self.K:
-                raise ValueError(f'{who}: results[{i}] has K = {kpts.shape[1]}, the smoother K = {self.K}')
-            if kpts.shape[0] > native.TRACK_MAX_POSES:
-                raise ValueError(f'{who}: results[{i}] has {kpts.shape[0]} poses, at most {native.TRACK_MAX_POSES}')
-            if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32
-                    and tuple(ids.shape) == (kpts.shape[0],)):
-                raise ValueError(f'{who}: ids of results[{i}] must be an int32 [{kpts.shape[0]}] tensor')
-            if not all(t is None or t.is_cuda for t in (kpts, bboxes, keep, ids)):
-                raise ValueError(f'{who}: results[{i}] and its ids must be HIP device tensors (pavenet_amd has no CPU '
-                                 'path)')
-            all_ids.append(ids.contiguous())
-        dev = poses[0][0].device
-        if self._state is not None and self._state['id'].device != dev:
-            raise ValueError(f"{who}: the smoother's state is on {self._state['id'].device}, results[0] on {dev}")
-        entries = [(kp, bb, keep, ids, c, sc) for (kp, bb, keep), ids, c, sc in zip(poses, all_ids, cams, scales)]
-        if self._state is None:
-            self._allocate(dev)
         outs = ops.smooth_poses(entries, self._state, max_age=self.max_age, alpha_min=self.alpha_min, beta=self.beta,
                                 velocity_gain=self.velocity_gain, score_thr=self.score_thr, kpt_thr=self.kpt_thr)
         results = []
@@ -114,19 +86,10 @@ class PoseSmoother:
     def reset(self, camera=None):
         """Frees the slots of `camera` (None: of every camera); its frame count and drop count restart at 0.  The
         state tensors stay where they are (a birth writes a slot's points, and a free slot's are never read)."""
-        if camera is not None:
-            camera = self._camera(camera, 'PoseSmoother.reset')
-        if self._state is None:
-            return
-        c = slice(None) if camera is None else camera
-        for name in ('id', 'frame', 'dropped'):
-            self._state[name][c] = 0
+        self._reset(camera)
 
     def state(self, camera=0):
         """Views of one camera's state on the device: id, last [S] (id 0 = free slot; its other fields mean
         nothing), pos, vel [S, K + 2, 2] (1/64 pixel and 1/64 pixel per frame; the key points, then the box corners;
         pos x < 0: the point is not initialised), frame, dropped (0-d).  None before the first call."""
-        camera = self._camera(camera, 'PoseSmoother.state')
-        if self._state is None:
-            return None
-        return {name: t[camera] for name, t in self._state.items()}
+        return self._views(camera, 'state', _STATE)

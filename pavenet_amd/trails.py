@@ -26,7 +26,8 @@ import torch
 from . import native, ops
 from .heatmap import MODES, _per_surface   # the (matrix, range) order of an NV12 launch's tables
 from .preprocess import NV12_MATRICES
-from .render import TRACK_PALETTE, _bgr_triple, _poses, _scales, bgr_to_yuv
+from .render import TRACK_PALETTE, _bgr_triple, bgr_to_yuv
+from .tracked import Tracked
 from .zones import ANKLES
 
 _STATE = ('id', 'last', 'pos', 'head', 'count', 'box', 'frame', 'dropped')
@@ -34,11 +35,12 @@ _POINTS = ('pts', 'when', 'head', 'count')
 _DRAWN = ('id', 'last', 'pos', 'head', 'count', 'box', 'pts', 'when', 'frame')
 
 
-class TrackTrails:
+class TrackTrails(Tracked):
     """Trails of `cameras` cameras: per track the last `length` (1 .. 64) committed points.  Who takes part, the slots
     (`max_tracks` 1 .. 128, freed after `max_age` frames unseen), `anchor`, `anchor_kpts`, `score_thr` and `kpt_thr`
     are ``ZoneMonitor``'s.  A track's anchor is committed when the newest committed point is at least `stride` (1 ..
     255) frames old and at least `min_step` (0 .. 65535) eighths of a pixel away in x or in y."""
+    _NOUN, _NOUNS = 'the trails', "the trails'"
 
     def __init__(self, K, cameras=1, max_tracks=128, max_age=30, length=32, stride=1, min_step=16, anchor='feet',
                  anchor_kpts=None, score_thr=0.3, kpt_thr=0.):
@@ -81,11 +83,6 @@ class TrackTrails:
                            pts=torch.zeros((C, S, L, 2), **z), when=torch.zeros((C, S, L), **z),
                            frame=torch.zeros((C,), **z), dropped=torch.zeros((C,), **z))
 
-    def _camera(self, camera, who):
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < self.cameras:
-            raise ValueError(f'{who}: camera must be an integer in [0, {self.cameras}), got {camera!r}')
-        return int(camera)
-
     def update_many(self, items, scale_factor=None):
         """items: (camera, result, ids) triples, the entries of one camera in time order -> one dict per item of new
         int32 [N] device tensors: count (the committed points of the pose's track), span (frames since the oldest of
@@ -93,36 +90,10 @@ class TrackTrails:
         along the committed points to the anchor); all 0 for a pose that takes no part.  result, ids and scale_factor
         are what `ZoneMonitor.update_many` takes.  One launch per 32 items on the current stream; no host copy, no
         sync."""
-        who = 'TrackTrails.update'
         items = list(items)
-        if any(not (isinstance(it, (tuple, list)) and len(it) == 3) for it in items):
-            raise ValueError(f'{who}: items are (camera, result, ids) triples')
-        if not items:
+        entries = self._entries(items, scale_factor, 'TrackTrails.update')
+        if not entries:
             return []
-        cams = [self._camera(c, who) for c, _, _ in items]
-        poses = [_poses(r, i, who) for i, (_, r, _) in enumerate(items)]
-        scales = _scales(scale_factor, len(items), who)
-        if any(not (0 < sx < float('inf') and 0 < sy < float('inf')) for sx, sy in scales):
-            raise ValueError(f'{who}: a scale factor must be positive and finite')
-        all_ids = []
-        for i, ((kpts, bboxes, keep), (_, _, ids)) in enumerate(zip(poses, items)):
-            if kpts.shape[1] != self.K:
-                raise ValueError(f'{who}: results[{i}] has K = {kpts.shape[1]}, the trails K = {self.K}')
-            if kpts.shape[0] > native.TRACK_MAX_POSES:
-                raise ValueError(f'{who}: results[{i}] has {kpts.shape[0]} poses, at most {native.TRACK_MAX_POSES}')
-            if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32
-                    and tuple(ids.shape) == (kpts.shape[0],)):
-                raise ValueError(f'{who}: ids of results[{i}] must be an int32 [{kpts.shape[0]}] tensor')
-            if not all(t is None or t.is_cuda for t in (kpts, bboxes, keep, ids)):
-                raise ValueError(f'{who}: results[{i}] and its ids must be HIP device tensors (pavenet_amd has no CPU '
-                                 'path)')
-            all_ids.append(ids.contiguous())
-        dev = poses[0][0].device
-        if self._state is not None and self._state['id'].device != dev:
-            raise ValueError(f"{who}: the trails' state is on {self._state['id'].device}, results[0] on {dev}")
-        entries = [(kp, bb, keep, ids, c, sc) for (kp, bb, keep), ids, c, sc in zip(poses, all_ids, cams, scales)]
-        if self._state is None:
-            self._allocate(dev)
         return ops.trail_update(entries, self._state, K=self.K, stride=self.stride, min_step=self.min_step,
                                 max_age=self.max_age, anchor=self.anchor, anchor_kpts=self.anchor_kpts,
                                 score_thr=self.score_thr, kpt_thr=self.kpt_thr)
@@ -134,30 +105,18 @@ class TrackTrails:
     def reset(self, camera=None):
         """Frees the slots of `camera` (None: of every camera) and restarts its frame and drop counts at 0.  The state
         tensors stay where they are."""
-        if camera is not None:
-            camera = self._camera(camera, 'TrackTrails.reset')
-        if self._state is None:
-            return
-        c = slice(None) if camera is None else camera
-        for name in ('id', 'frame', 'dropped'):
-            self._state[name][c] = 0
+        self._reset(camera)
 
     def state(self, camera=0):
         """Views of one camera's slots on the device: id, last, head, count [S], pos [S, 2], box [S, 4] (id 0 = free
         slot; its other fields mean nothing), frame, dropped (0-d); 1/8 pixel.  None before the first call."""
-        camera = self._camera(camera, 'TrackTrails.state')
-        if self._state is None:
-            return None
-        return {name: self._state[name][camera] for name in _STATE}
+        return self._views(camera, 'state', _STATE)
 
     def points(self, camera=0):
         """Views of one camera's rings on the device: pts [S, L, 2] (1/8 pixel), when [S, L] (the frame a point was
         committed in), head and count [S]: slot t's committed points are, oldest first, pts[t, (head - count + 1 + j) %
         L] for j = 0 .. count - 1.  None before the first call."""
-        camera = self._camera(camera, 'TrackTrails.points')
-        if self._state is None:
-            return None
-        return {name: self._state[name][camera] for name in _POINTS}
+        return self._views(camera, 'points', _POINTS)
 
     def device_tensors(self):
         """The whole tensors a reader on the device needs, for every camera at once and read only (what

@@ -19,7 +19,7 @@ import math
 import torch
 
 from . import native, ops
-from .render import _poses, _scales
+from .tracked import Tracked
 
 ENTER, EXIT, DWELL, APPEAR, VANISH, CROSS_FWD, CROSS_BACK = (
     native.DEFINES['PAVE_ZONE_' + n] for n in ('ENTER', 'EXIT', 'DWELL', 'APPEAR', 'VANISH', 'CROSS_FWD', 'CROSS_BACK'))
@@ -77,7 +77,7 @@ def quantise_geometry(zones, lines, dwell_frames=None, who='ZoneMonitor.set_zone
     return row
 
 
-class ZoneMonitor:
+class ZoneMonitor(Tracked):
     """Relates the tracks of `cameras` cameras to places: per camera up to 8 polygonal zones and 8 directed counting
     lines (`set_zones`), one slot per track id (`max_tracks`, 1 .. 128; a slot not seen for more than `max_age`
     frames is freed).  A pose takes part iff its box score is > `score_thr` (and keep, and finite coordinates), its id
@@ -88,6 +88,8 @@ class ZoneMonitor:
     visible, 'box' always that bottom centre, 'centre' the centre of the box.  A track's zone bit flips once the
     inside test has disagreed with it `min_frames` (1 .. 255) frames in a row; a line crossing is not debounced.
     `max_events` (1 .. 4096) rows of events are stored per frame, and all of them are counted."""
+    _NOUN, _NOUNS = 'the monitor', "the monitor's"
+    _RESET = ('id', 'frame', 'dropped', 'counters')
 
     def __init__(self, K, cameras=1, max_tracks=128, max_age=30, anchor='feet', anchor_kpts=None, min_frames=2,
                  max_events=256, score_thr=0.3, kpt_thr=0.):
@@ -131,11 +133,6 @@ class ZoneMonitor:
                            counters=torch.zeros((C, native.ZONE_COUNTER_WORDS), **z),
                            geometry=torch.zeros((C, native.ZONE_GEOM_WORDS), **z))
 
-    def _camera(self, camera, who):
-        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < self.cameras:
-            raise ValueError(f'{who}: camera must be an integer in [0, {self.cameras}), got {camera!r}')
-        return int(camera)
-
     def set_zones(self, camera, zones=(), lines=(), dwell_frames=None):
         """The geometry of `camera`, in original-image pixels (0 .. 8191): `zones` polygons of 3 .. 16 (x, y)
         vertices (even-odd, so a polygon may be concave), at most 8; `lines` ((ax, ay), (bx, by)) pairs, at most 8 --
@@ -159,36 +156,10 @@ class ZoneMonitor:
         where it is not), events [max_events, 5] (rows (kind, index, id, pose, frame) in the rule's order; zero
         past the count) and n_events (0-d: all events of the frame, stored or not).  result, ids and scale_factor
         are what `PoseSmoother.smooth_many` takes.  One launch per 32 items."""
-        who = 'ZoneMonitor.update'
         items = list(items)
-        if any(not (isinstance(it, (tuple, list)) and len(it) == 3) for it in items):
-            raise ValueError(f'{who}: items are (camera, result, ids) triples')
-        if not items:
+        entries = self._entries(items, scale_factor, 'ZoneMonitor.update')
+        if not entries:
             return []
-        cams = [self._camera(c, who) for c, _, _ in items]
-        poses = [_poses(r, i, who) for i, (_, r, _) in enumerate(items)]
-        scales = _scales(scale_factor, len(items), who)
-        if any(not (0 < sx < float('inf') and 0 < sy < float('inf')) for sx, sy in scales):
-            raise ValueError(f'{who}: a scale factor must be positive and finite')
-        all_ids = []
-        for i, ((kpts, bboxes, keep), (_, _, ids)) in enumerate(zip(poses, items)):
-            if kpts.shape[1] != self.K:
-                raise ValueError(f'{who}: results[{i}] has K = {kpts.shape[1]}, the monitor K = {self.K}')
-            if kpts.shape[0] > native.TRACK_MAX_POSES:
-                raise ValueError(f'{who}: results[{i}] has {kpts.shape[0]} poses, at most {native.TRACK_MAX_POSES}')
-            if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32
-                    and tuple(ids.shape) == (kpts.shape[0],)):
-                raise ValueError(f'{who}: ids of results[{i}] must be an int32 [{kpts.shape[0]}] tensor')
-            if not all(t is None or t.is_cuda for t in (kpts, bboxes, keep, ids)):
-                raise ValueError(f'{who}: results[{i}] and its ids must be HIP device tensors (pavenet_amd has no CPU '
-                                 'path)')
-            all_ids.append(ids.contiguous())
-        dev = poses[0][0].device
-        if self._state is not None and self._state['id'].device != dev:
-            raise ValueError(f"{who}: the monitor's state is on {self._state['id'].device}, results[0] on {dev}")
-        entries = [(kp, bb, keep, ids, c, sc) for (kp, bb, keep), ids, c, sc in zip(poses, all_ids, cams, scales)]
-        if self._state is None:
-            self._allocate(dev)
         return ops.zone_events(entries, self._state, K=self.K, max_age=self.max_age, anchor=self.anchor,
                                anchor_kpts=self.anchor_kpts, min_frames=self.min_frames, max_events=self.max_events,
                                score_thr=self.score_thr, kpt_thr=self.kpt_thr)
@@ -201,13 +172,7 @@ class ZoneMonitor:
         """Frees the slots of `camera` (None: of every camera) without events; its frame count, drop count and
         counters restart at 0 and its geometry stays.  The state tensors stay where they are (a birth writes a
         slot, and a free slot is never read)."""
-        if camera is not None:
-            camera = self._camera(camera, 'ZoneMonitor.reset')
-        if self._state is None:
-            return
-        c = slice(None) if camera is None else camera
-        for name in ('id', 'frame', 'dropped', 'counters'):
-            self._state[name][c] = 0
+        self._reset(camera)
 
     def counts(self, camera=0):
         """Views of one camera's running counters on the device: occupancy, entered, exited, appeared, vanished [8]
@@ -226,10 +191,7 @@ class ZoneMonitor:
         """Views of one camera's state on the device: id, last, inside, alerted [S] (id 0 = free slot; its other
         fields mean nothing), pos [S, 2] (1/8 pixel), streak, since [S, 8], frame, dropped (0-d).  None before the
         first call."""
-        camera = self._camera(camera, 'ZoneMonitor.state')
-        if self._state is None:
-            return None
-        return {name: self._state[name][camera] for name in _STATE}
+        return self._views(camera, 'state', _STATE)
 
     def device_tensors(self):
         """The whole tensors a reader on the device needs, for every camera at once and read only: geometry

@@ -6,7 +6,8 @@
 Compiles each translation unit of build_native.SOURCES in both flavours (shipped, -DPAVE_DIAG=1) with
 build_native's flags plus --cuda-device-only, unbundles the gfx950 code object and compares .text as a
 whole; where that differs (instantiation order moved), every FUNC symbol's name, size and code bytes
-and every .kd descriptor.  Prints one line per file and flavour; exit status 1 on any difference."""
+and every .kd descriptor.  Where a function's code differs the line says whether its descriptor (registers, LDS,
+scratch) differs too.  Prints one line per file and flavour; exit status 1 on any difference."""
 import argparse
 import concurrent.futures
 import hashlib
@@ -15,8 +16,11 @@ import subprocess
 import sys
 import tempfile
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+from pavenet_amd import build_native   # noqa: E402
+
 LLVM = os.environ.get('ROCM_LLVM', '/opt/rocm/llvm/bin')
-UNITS = ['pave_kernels', 'pave_gemm_split', 'pave_enc_tile', 'pave_gemm_dma', 'pave_decoder', 'pave_aug']
+UNITS = [os.path.splitext(os.path.basename(src))[0] for src in build_native.SOURCES]
 TARGET = 'hipv4-amdgcn-amd-amdhsa--gfx950'
 
 
@@ -68,7 +72,14 @@ def compare(old, new, unit, defs, tmp):
     bad = sorted(s for s in set(a) | set(b) if a.get(s) != b.get(s))
     if not bad:
         return True, '%s identical per symbol (order moved): %d kernels, %d symbols' % (label, kernels, len(a))
-    return False, '%s DIFFERS in %d of %d symbols: %s' % (label, len(bad), len(set(a) | set(b)), ', '.join(bad[:6]))
+    notes = []
+    for s in bad:
+        if not s.endswith('.kd'):
+            kd = 'absent' if s + '.kd' not in a else 'differs' if s + '.kd' in bad else 'identical'
+            notes.append('%s (%s -> %s bytes, .kd %s)' % (s, a[s][0] if s in a else '-', b[s][0] if s in b else '-', kd))
+        elif s[:-3] not in bad:
+            notes.append(s + ' (code identical)')
+    return False, '%s DIFFERS in %d of %d symbols: %s' % (label, len(bad), len(set(a) | set(b)), ', '.join(notes))
 
 
 def main():
