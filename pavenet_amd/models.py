@@ -110,6 +110,7 @@ def petr_r50_cfg(num_keypoints=17, num_query=300, max_per_img=100, head='opera.P
             sync_cls_avg_factor=True, with_kpt_refine=True, as_two_stage=True,
             transformer=dict(
                 type='opera.PETRTransformer', num_keypoints=K, encoder=enc(4),
+                two_stage_num_proposals=num_query,   # (one proposal per query embedding row)
                 decoder=dict(type='opera.PetrTransformerDecoder', num_keypoints=K, num_layers=3,
                              return_intermediate=True,
                              transformerlayers=_decoder_layer(

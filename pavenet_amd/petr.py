@@ -296,6 +296,8 @@ class PETRHead(BaseModule):
         det_kpts = r_kpts[-1].view(B, N, K, 2)
         if taps is not None:
             taps.update(score_topk=indexs, refine_hs=r_hs, refine_kpts=det_kpts.clone())
+            if self.with_sigma:
+                taps['refine_sigma'] = r_sigmas[-1].view(B, N, K, 2)
         dev = det_kpts.device
         wh, sf = self._meta_scales(img_metas, dev)
         det_kpts = torch.minimum((det_kpts * wh).clamp(min=0), wh)
