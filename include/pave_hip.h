@@ -1247,6 +1247,86 @@ typedef struct pave_floor_plan {
 int pave_floor_update(const pave_floor_plan* plan, void* stream);
 
 /*
+ * Contacts and groups on the floor: which tracks stand within a radius of each other, debounced with hysteresis, for
+ * how long, which parties they form (the connected components of the contact graph), and the MEET / PART / LONG
+ * events of the frame (pavenet_amd/csrc/pave_contacts.hip; the rule is DESIGN section 24, integer-exact).  It takes
+ * what pave_floor_update wrote: the `on` and `xy` sections of its output.  The plan is copied into the kernel's
+ * arguments.
+ *
+ * pave_contact_update: one launch for `entries` frames of any of `cameras` cameras; one block per camera of the launch
+ * takes that camera's entries in plan order, as pave_floor_update does: entries of one camera are in time order.
+ *   on[i]            DEVICE [n[i]] int32, read: != 0: the pose is placed on the floor
+ *   xy[i]            DEVICE [n[i], 2] int32, read: its floor position in mm (read clamped to +-PAVE_FLOOR_MAX_MM, so a
+ *                    squared distance is below 2^44)
+ *   ids[i]           DEVICE [n[i]] int32, read: the track ids of the frame; a pose takes part iff on, id >= 1 and no
+ *                    pose before it that passes both tests has its id (all three may be NULL where n[i] == 0)
+ *   n[i]             0 .. PAVE_TRACK_MAX_POSES;  camera[i] in [0, cameras)
+ *   out[i]           DEVICE [PAVE_CONTACT_OUT_WORDS * n[i]] int32, out: group [n] (the smallest track id of the pose's
+ *                    component), size [n] (its slots), contacts [n] (the pose's degree), partner [n] (the id of its
+ *                    contact of the smallest since, the lower slot on a tie, or 0), together [n] (frames since that
+ *                    contact began, or 0), one after the other; all 0 for a pose without a slot (may be NULL where n[i]
+ *                    == 0)
+ *   out_events[i]    DEVICE [max_events, PAVE_CONTACT_EVENT_WORDS] int32, out: rows (kind, a, b, frames, pose_a, pose_b,
+ *                    frame), a < b the two track ids, pose_* their rows in this frame or -1: first the PARTs of the
+ *                    slots that expired, in ascending (s, t) of the slot pair, then the MEET, PART and LONG of the
+ *                    pairs of live slots in ascending (s, t); zero past the count
+ *   out_n_events[i]  DEVICE [1] int32, out: all events of the frame, stored or not
+ *   the state, DEVICE int32, read and written: slot_id, slot_last [cameras, S] (id 0: a free slot, its other fields
+ *                    are never read), slot_pos [cameras, S, 2] (mm); link, since [cameras, S, S]: the words of the slot
+ *                    pair s < t at [s, t] (link bit 0: in contact, bits 8 ..: the frames in a row the distance test has
+ *                    disagreed with it; since: the frame the contact began, 0 without one), read only while both slots
+ *                    are live, zeroed when either is born; frame, dropped [cameras]; counters [cameras,
+ *                    PAVE_CONTACT_COUNTER_WORDS]: PAVE_CONTACT_CNT_*
+ *   radius           0 .. 2^20 mm: two tracks not in contact are near iff dx^2 + dy^2 <= radius^2
+ *   release          radius .. 2^21 mm: two tracks in contact are near iff dx^2 + dy^2 <= release^2
+ *   min_frames       1 .. 255: the contact bit flips once near has disagreed with it this many frames in a row
+ *   long_frames      0 .. 2^30: a contact of exactly this many frames is reported once (0: never)
+ *   max_events       1 .. 4096 rows of out_events[i];  max_age >= 0: a slot unseen for more frames is freed
+ * Refused with PAVE_E_ARG before any device call: a null plan, entries outside 1 .. 32, S outside 1 .. 128, cameras
+ * outside 1 .. 4096, a null state or output tensor, a null input where n[i] > 0, n[i] outside 0 .. 128, a camera index
+ * outside [0, cameras), radius, release, min_frames, long_frames or max_events outside their ranges, max_age < 0.  A
+ * slot index is a loop counter below S and a pose index is below n[i]: a plan that passes cannot address memory
+ * outside its tensors, whatever the inputs and the state hold.
+ */
+#define PAVE_CONTACT_MEET 1
+#define PAVE_CONTACT_PART 2
+#define PAVE_CONTACT_LONG 3
+#define PAVE_CONTACT_OUT_WORDS 5
+#define PAVE_CONTACT_EVENT_WORDS 7
+#define PAVE_CONTACT_COUNTER_WORDS 8
+#define PAVE_CONTACT_CNT_CONTACTS 0
+#define PAVE_CONTACT_CNT_MEETS 1
+#define PAVE_CONTACT_CNT_PARTS 2
+#define PAVE_CONTACT_CNT_LONGS 3
+#define PAVE_CONTACT_CNT_GROUPS 4
+#define PAVE_CONTACT_CNT_GROUPED 5
+#define PAVE_CONTACT_CNT_LARGEST 6
+#define PAVE_CONTACT_MAX_RADIUS 1048576
+#define PAVE_CONTACT_MAX_RELEASE 2097152
+#define PAVE_CONTACT_MAX_LONG 1073741824
+#define PAVE_CONTACT_MAX_EVENTS 4096
+typedef struct pave_contact_plan {
+  const int32_t* on[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* xy[PAVE_TRACK_MAX_FRAMES];
+  const int32_t* ids[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_events[PAVE_TRACK_MAX_FRAMES];
+  int32_t*       out_n_events[PAVE_TRACK_MAX_FRAMES];
+  int            n[PAVE_TRACK_MAX_FRAMES];
+  int            camera[PAVE_TRACK_MAX_FRAMES];
+  int32_t* slot_id;
+  int32_t* slot_last;
+  int32_t* slot_pos;
+  int32_t* link;
+  int32_t* since;
+  int32_t* frame;
+  int32_t* dropped;
+  int32_t* counters;
+  int entries, cameras, S, radius, release, min_frames, long_frames, max_events, max_age;
+} pave_contact_plan;
+int pave_contact_update(const pave_contact_plan* plan, void* stream);
+
+/*
  * 3x3 convolution, NHWC fp32, pad 1, stride 1 or 2, bias (+ReLU) fused: implicit GEMM on the
  * exact-fp32 MFMA.  Used for the ResNet / HRNet 3x3 convolutions with BatchNorm folded in
  * (mmdet resnet.py Bottleneck.conv2 / BasicBlock, hrnet.py).

@@ -62,6 +62,9 @@ def __getattr__(name):
     if name == 'GroundPlane':
         from . import floor
         return floor.GroundPlane
+    if name == 'ContactMonitor':
+        from . import contacts
+        return contacts.ContactMonitor
     if name == 'PersonReID':
         from . import reid
         return reid.PersonReID

@@ -30,6 +30,7 @@ SOURCES = [os.path.join(_HERE, 'csrc', 'pave_kernels.hip'),
            os.path.join(_HERE, 'csrc', 'pave_heat.hip'),
            os.path.join(_HERE, 'csrc', 'pave_trails.hip'),
            os.path.join(_HERE, 'csrc', 'pave_floor.hip'),
+           os.path.join(_HERE, 'csrc', 'pave_contacts.hip'),
            os.path.join(_HERE, 'csrc', 'pave_reid.hip'),
            os.path.join(_HERE, 'csrc', 'pave_anon.hip')]
 HEADERS = sorted(os.path.join(_HERE, 'csrc', f) for f in os.listdir(os.path.join(_HERE, 'csrc')) if f.endswith('.h')) + \

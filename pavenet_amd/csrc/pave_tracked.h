@@ -1,6 +1,7 @@
 // What every update that follows track ids through per-camera slots has in common, once:
-// smooth_poses_kernel, zone_events_kernel, posture_events_kernel, heat_update_kernel, trail_update_kernel and
-// floor_update_kernel are built from these steps, and the units that only quantise take quant from here.
+// smooth_poses_kernel, zone_events_kernel, posture_events_kernel, heat_update_kernel, trail_update_kernel,
+// floor_update_kernel and contact_update_kernel are built from these steps, and the units that only quantise take quant
+// from here.
 //
 // A coordinate becomes quarter pixels as in sections 13 and 14,
 //   X = clamp((int)rintf((x / sx) * 4.f), 0, 32767)     (correctly rounded division, no contraction).

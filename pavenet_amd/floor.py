@@ -15,9 +15,13 @@ integer-exact and nothing is read on the host.
 ``out['floor']`` is for the consumers that stand a pose on its anchor only: every key point and the box of a pose are
 that one point.  It is not for ``PostureMonitor``, ``draw_poses_*``, ``anonymize_*`` or ``PoseTracker``.
 
+``nearest``, ``gap`` and ``near`` are one frame's answer.  Who stands with whom over time -- debounced pair contacts,
+how long they last and the groups they form -- is ``contacts.ContactMonitor``, which takes the dict
+``update`` returns.
+
 Not built: lens distortion (undistort the calibration marks and accept the error, or calibrate close to where people
-walk); calibration from vanishing points; debounced pair-contact events and groups; identity across cameras; smoothing
-of the floor position (feed ``PoseSmoother``'s result); a plan-view draw of its own.
+walk); calibration from vanishing points; identity across cameras; smoothing of the floor position (feed
+``PoseSmoother``'s result); a plan-view draw of its own.
 """
 import math
 

@@ -384,6 +384,27 @@ class FloorPlan(ctypes.Structure):
                 ('max_age', ctypes.c_int), ('score_thr', ctypes.c_float), ('kpt_thr', ctypes.c_float)]
 
 
+CONTACT_OUT_WORDS, CONTACT_EVENT_WORDS, CONTACT_COUNTER_WORDS = (
+    DEFINES['PAVE_CONTACT_' + n] for n in ('OUT_WORDS', 'EVENT_WORDS', 'COUNTER_WORDS'))
+CONTACT_MAX_RADIUS, CONTACT_MAX_RELEASE, CONTACT_MAX_LONG, CONTACT_MAX_EVENTS = (
+    DEFINES['PAVE_CONTACT_MAX_' + n] for n in ('RADIUS', 'RELEASE', 'LONG', 'EVENTS'))
+
+
+class ContactPlan(ctypes.Structure):
+    """`pave_contact_plan` of include/pave_hip.h (the by-value argument of pave_contact_update)."""
+    _fields_ = [('on', ctypes.c_void_p * TRACK_MAX_FRAMES), ('xy', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('ids', ctypes.c_void_p * TRACK_MAX_FRAMES), ('out', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_events', ctypes.c_void_p * TRACK_MAX_FRAMES),
+                ('out_n_events', ctypes.c_void_p * TRACK_MAX_FRAMES), ('n', ctypes.c_int * TRACK_MAX_FRAMES),
+                ('camera', ctypes.c_int * TRACK_MAX_FRAMES), ('slot_id', ctypes.c_void_p),
+                ('slot_last', ctypes.c_void_p), ('slot_pos', ctypes.c_void_p), ('link', ctypes.c_void_p),
+                ('since', ctypes.c_void_p), ('frame', ctypes.c_void_p), ('dropped', ctypes.c_void_p),
+                ('counters', ctypes.c_void_p), ('entries', ctypes.c_int), ('cameras', ctypes.c_int),
+                ('S', ctypes.c_int), ('radius', ctypes.c_int), ('release', ctypes.c_int),
+                ('min_frames', ctypes.c_int), ('long_frames', ctypes.c_int), ('max_events', ctypes.c_int),
+                ('max_age', ctypes.c_int)]
+
+
 _lib = None
 
 

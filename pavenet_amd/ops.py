@@ -1694,6 +1694,102 @@ def floor_update(entries, state, calib, *, K, velocity_gain=4, near=1500, unit=1
     return outs
 
 
+_CONTACT_STATE = (('id', 1), ('last', 1), ('pos', 2), ('link', 3), ('since', 3), ('frame', 0), ('dropped', 0),
+                  ('counters', 4))
+# name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, S], 4 [cameras, 8]
+CONTACT_OUTPUTS = ('group', 'size', 'contacts', 'partner', 'together')      # the [N] sections of one launch output
+
+
+def contact_update(entries, state, *, radius=1500, release=None, min_frames=3, long_frames=0, max_events=256,
+                   max_age=30):
+    """Debounced pair contacts, their durations, the groups they form and the frame's events from frames of floor
+    positions, one launch per 32 frames (pave_contact_update; the rule is DESIGN section 24).  entries: one (on [N]
+    int32, xy [N, 2] int32 mm, ids [N] int32, camera) per frame -- `floor_update`'s on and xy and the frame's track ids
+    -- N <= 128, the frames of one camera in time order; state: int32 device tensors id, last [cameras, S], pos
+    [cameras, S, 2], link, since [cameras, S, S], frame, dropped [cameras] and counters [cameras, 8]
+    (PAVE_CONTACT_CNT_* of include/pave_hip.h), read and written; radius 0 .. 2^20 mm, release radius .. 2^21 mm (None:
+    radius), min_frames 1 .. 255, long_frames 0 .. 2^30 (0: never), max_events 1 .. 4096.  Returns one dict(group, size,
+    contacts, partner, together [N], events [max_events, 7], n_events 0-d) per entry, int32 views of one new
+    allocation.  Shapes, types and ranges raise ValueError before anything is asked of a device."""
+    who = 'contact_update'
+    entries = list(entries)
+    names = [n for n, _ in _CONTACT_STATE]
+    if not isinstance(state, dict) or any(not isinstance(state.get(name), torch.Tensor) for name in names):
+        raise ValueError(f'{who}: state holds the tensors {", ".join(names)}')
+    if state['id'].dim() != 2:
+        raise ValueError(f'{who}: state id must be [cameras, S], got {tuple(state["id"].shape)}')
+    cameras, S = state['id'].shape
+    if not (1 <= cameras <= native.TRACK_MAX_CAMERAS and 1 <= S <= native.TRACK_MAX_TRACKS):
+        raise ValueError(f'{who}: cameras in 1 .. {native.TRACK_MAX_CAMERAS} and S in 1 .. {native.TRACK_MAX_TRACKS}, got '
+                         f'{cameras} and {S}')
+    for name, kind in _CONTACT_STATE:
+        t = state[name]
+        want = ((cameras,), (cameras, S), (cameras, S, 2), (cameras, S, S), (cameras, native.CONTACT_COUNTER_WORDS))[kind]
+        if t.dtype != torch.int32 or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f'{who}: state {name} must be a contiguous int32 {list(want)} tensor')
+    _int_in(who, 'radius', radius, 0, native.CONTACT_MAX_RADIUS)
+    if release is None:
+        release = radius
+    _int_in(who, 'release', release, radius, native.CONTACT_MAX_RELEASE)
+    _int_in(who, 'min_frames', min_frames, 1, 255)
+    _int_in(who, 'long_frames', long_frames, 0, native.CONTACT_MAX_LONG)
+    _int_in(who, 'max_events', max_events, 1, native.CONTACT_MAX_EVENTS)
+    max_age = _max_age(who, max_age)
+    checked = []
+    for i, entry in enumerate(entries):
+        if not (isinstance(entry, (tuple, list)) and len(entry) == 4):
+            raise ValueError(f'{who}: entry {i} is (on, xy, ids, camera)')
+        on, xy, ids, camera = entry
+        if not (isinstance(on, torch.Tensor) and on.dtype == torch.int32 and on.dim() == 1):
+            raise ValueError(f'{who}: on of entry {i} must be a [N] int32 tensor')
+        N = on.shape[0]
+        if not (isinstance(xy, torch.Tensor) and xy.dtype == torch.int32 and tuple(xy.shape) == (N, 2)):
+            raise ValueError(f'{who}: xy of entry {i} must be a [{N}, 2] int32 tensor')
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and tuple(ids.shape) == (N,)):
+            raise ValueError(f'{who}: ids of entry {i} must be a [{N}] int32 tensor')
+        if N > native.TRACK_MAX_POSES:
+            raise ValueError(f'{who}: entry {i} has {N} poses, at most {native.TRACK_MAX_POSES}')
+        if isinstance(camera, bool) or int(camera) != camera or not 0 <= camera < cameras:
+            raise ValueError(f'{who}: the camera of entry {i} must be an integer in [0, {cameras}), got {camera!r}')
+        if not (on.is_contiguous() and xy.is_contiguous() and ids.is_contiguous()):
+            raise ValueError(f'{who}: the tensors of entry {i} must be contiguous')
+        checked.append((on, xy, ids, int(camera), N))
+    # the shapes are right: now where the tensors live
+    dev = state['id'].device
+    if not dev.type == 'cuda':
+        raise ValueError(f'{who}: the state must be on a HIP device (pavenet_amd has no CPU path), got {dev}')
+    if any(state[n].device != dev for n in names):
+        raise ValueError(f'{who}: the state tensors must be on one device ({dev})')
+    for i, c in enumerate(checked):
+        if c[0].device != dev or c[1].device != dev or c[2].device != dev:
+            raise ValueError(f'{who}: the tensors of entry {i} must be on the HIP device of the state ({dev})')
+    OW, EW = native.CONTACT_OUT_WORDS, native.CONTACT_EVENT_WORDS
+    words = [torch.empty((OW * c[4] + EW * max_events + 1,), dtype=torch.int32, device=dev) for c in checked]
+    for at in range(0, len(checked), native.TRACK_MAX_FRAMES):
+        plan = native.ContactPlan()
+        part = checked[at:at + native.TRACK_MAX_FRAMES]
+        for i, (on, xy, ids, camera, N) in enumerate(part):
+            base = words[at + i].data_ptr()
+            plan.on[i], plan.xy[i], plan.ids[i] = on.data_ptr() or None, xy.data_ptr() or None, ids.data_ptr() or None
+            plan.out[i] = base if N else None
+            plan.out_events[i], plan.out_n_events[i] = base + 4 * OW * N, base + 4 * (OW * N + EW * max_events)
+            plan.n[i], plan.camera[i] = N, camera
+        (plan.slot_id, plan.slot_last, plan.slot_pos, plan.link, plan.since, plan.frame, plan.dropped,
+         plan.counters) = (state[n].data_ptr() for n in names)
+        plan.entries, plan.cameras, plan.S, plan.max_age = len(part), cameras, S, max_age
+        plan.radius, plan.release, plan.min_frames = radius, release, min_frames
+        plan.long_frames, plan.max_events = long_frames, max_events
+        _launch('pave_contact_update', who, dev, ctypes.byref(plan))
+    outs = []
+    for c, w in zip(checked, words):
+        N = c[4]
+        out = {name: w[i * N:(i + 1) * N] for i, name in enumerate(CONTACT_OUTPUTS)}
+        out['events'] = w[OW * N:OW * N + EW * max_events].view(max_events, EW)
+        out['n_events'] = w[OW * N + EW * max_events]
+        outs.append(out)
+    return outs
+
+
 _REID_STATE =(('person', 1), ('track', 1), ('last', 1), ('hits', 2), ('hist', 3), ('frame', 0), ('next', 0),
                ('dropped', 0))   # name, kind: 0 [cameras], 1 [cameras, S], 2 [cameras, S, 2], 3 [cameras, S, 2, 256]
 

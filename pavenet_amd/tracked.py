@@ -1,8 +1,9 @@
 """What the classes that follow track ids through per-camera slots share (the device side is
 ``csrc/pave_tracked.h``): ``PoseSmoother``, ``ZoneMonitor``, ``PostureMonitor``, ``FootfallMap``, ``TrackTrails`` and
 ``GroundPlane`` take the same (camera, result, ids) items, turn them into the entries of one ``ops`` call in the same
-way, and reset and show a state of named int32 tensors whose first axis is the camera.  ``PoseTracker`` and
-``PersonReID`` take other items and are not built on this.
+way, and reset and show a state of named int32 tensors whose first axis is the camera.  ``ContactMonitor`` takes
+``GroundPlane``'s output and not a result: it checks its items itself and shares the camera check, the reset and the
+views.  ``PoseTracker`` and ``PersonReID`` take other items and are not built on this.
 """
 import torch
 
